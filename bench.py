@@ -9,10 +9,19 @@ verify + ordered tuples left in HBM.  Weak scaling: rank r replays its own 64 se
 only for the barrier and the max-over-ranks timing).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+                                     a plain run: set-up, W warm-up steps, K timed steps, the result
+                                     line (the legs of --full are null in it)
                                      --gpus N > 1 without WORLD_SIZE in the environment: the parent
                                      (which never touches a GPU) launches N ranks with
                                      torch.distributed.run and exits with their status; under a
                                      launcher WORLD_SIZE must equal N
+  python bench.py --full             after the timed steps, the replay bench's other legs (1 GPU): the CPU
+                                     baselines, the end-to-end rates from pageable and pinned host memory,
+                                     the index rebuild, the device index and kvs_open from files
+                                     (--no-cpu / --no-stream / --no-open drop single legs)
+  python bench.py --dump-outputs DIR after the timed steps, what the last timed step computed, as
+                                     DIR/<name>.npy (float64; a fixed seeded sample of a large output plus
+                                     whole-output sums), for comparing two builds output for output
   python bench.py --dry-run          the same launch / barrier / max-over-ranks path on CPU (gloo), a
                                      sleep standing in for the replay (tests/test_bench_launch.py)
   python bench.py --mode etag        batch ETag compute/verify in cfg3's volume-server
@@ -58,12 +67,20 @@ def main():
     ap.add_argument("--segments", type=int, default=0, help="override segments per GPU")
     ap.add_argument("--cpu-segs", type=int, default=0,
                     help="CPU baseline sample in segments (default: about 2 GiB of the shard)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-stream", action="store_true", help="skip the pinned-host streamed (H2D-inclusive) leg")
-    ap.add_argument("--no-open", action="store_true", help="skip the kvs_open-from-files leg")
+    ap.add_argument("--full", action="store_true",
+                    help="replay mode, 1 GPU: also run the legs beside the headline figure (CPU baselines, "
+                         "host end-to-end, streamed, index rebuild, device index, kvs_open from files)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and host end-to-end legs")
+    ap.add_argument("--no-stream", action="store_true",
+                    help="with --full: skip the pinned-host streamed (H2D-inclusive) and device index legs")
+    ap.add_argument("--no-open", action="store_true", help="with --full: skip the kvs_open-from-files leg")
     ap.add_argument("--stream-batch", type=int, default=512 << 20, help="kvr_replay_stream batch bytes")
     ap.add_argument("--dry-run", action="store_true", help="CPU rehearsal of the launch and timing path (gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.config is None:
         args.config = "cfg4" if args.mode == "compact" else "cfg2"
 
@@ -132,11 +149,14 @@ def main():
             raise RuntimeError(f"replay failed: status {r.status} error {r.error and r.error.kind}")
         return r
 
+    r = None
     for _ in range(args.warmup):
         r = step()
     # correctness of the timed work: every record present and CRC-verified against the manifest
-    assert r.n == n_rec, (r.n, n_rec)
-    assert r.stats.n_crc_fail == 0
+    # (checked on the last timed step too, below)
+    if r is not None:
+        assert r.n == n_rec, (r.n, n_rec)
+        assert r.stats.n_crc_fail == 0
 
     if world > 1:
         dist.barrier()
@@ -155,6 +175,14 @@ def main():
         from kvreplay.shard import max_over_ranks
         per_rank = gather_per_rank(dt, seg_total, args.steps)
         dt = max_over_ranks(dt)
+    assert r.n == n_rec and r.stats.n_crc_fail == 0, (r.n, n_rec, r.stats.n_crc_fail)
+    if args.dump_outputs:
+        # the caller's view of the last timed step: the ordered tuples in HBM and the counts
+        tup = out[: r.n * 32].cpu().numpy().view(K.TUPLE_DTYPE)
+        dump_outputs(args.dump_outputs, rank, world, {
+            "replay_summary": [r.status, r.n, r.stats.n_crc_fail],
+            **tuple_arrays("tuples", tup)})
+        del tup
 
     ms_replay = float(np.mean([a for a, _ in k_ms]))
     ms_pipe = float(np.mean([b for _, b in k_ms]))
@@ -164,8 +192,10 @@ def main():
     alg_bytes = seg_total + 32 * n_rec          # segment bytes read once + 32-B tuple writes
     achieved = alg_bytes / (ms_replay / 1e3) / 1e9
 
+    # everything below the headline figure runs only with --full (1 GPU)
+    legs = args.full and rank == 0 and world == 1
     cpu = e2e = cpu_par = cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if legs and not args.no_cpu:
         import oracle_py as O   # the checker / CPU baseline only
         # the faithful port runs about 0.5 GiB/s on one core: a sample of about 2 GiB (32 of cfg2's
         # 64 segments, 4 of cfg5's 512-MiB segments, 2 of cfg3's 1-GiB segments) keeps it near 5 s
@@ -224,7 +254,7 @@ def main():
                          f"(engine.rs:79-154 cost model), 1 thread, warm memory; the map is released after the clock"}
 
     stream = None
-    if rank == 0 and world == 1 and not args.no_stream:
+    if legs and not args.no_stream:
         # H2D-inclusive rate (SURVEY §8d end-to-end, §8f rank 2): the whole shard in pinned host
         # memory, streamed through kvr_replay_stream (batch b+1's DMA overlapping batch b's replay),
         # tuples back in host memory with the CRC verification; wall clock of the whole call
@@ -277,7 +307,7 @@ def main():
         del pin
 
     live_idx = None
-    if rank == 0 and world == 1 and not args.no_stream:
+    if legs and not args.no_stream:
         # the index built on the device (kvr_replay_live: replay + last-writer fold in HBM, only
         # the live keys' final tuples written), device-resident in and out
         lo = torch.empty((n_rec + 1024) * 32, dtype=torch.uint8, device=dev)
@@ -297,7 +327,7 @@ def main():
         del lo
 
     open_files = None
-    if rank == 0 and world == 1 and not args.no_open:
+    if legs and not args.no_open:
         # KVStore::open from files (engine.rs:24-76): the shard written as segment-<id>.dat files
         # (page cache warm), then kvs_open_ex: parallel pread into pinned memory, per-segment DMA
         # into HBM as each file lands, replay + fold + key table on the device; best of 2
@@ -409,6 +439,11 @@ def bench_compact(args, ctx, segs, seg_nos, seg_total, n_rec, desc, nseg, seg_by
         st.append((r.stats.ms_replay, r.stats.ms_fold, r.stats.ms_gather))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, 0, 1, {
+            "compact_summary": [r.status, r.out_len, r.n_segs, r.stats.n_live],
+            "compact_seg_ends": r.seg_ends,
+            **byte_arrays("compact_bytes", out[: r.out_len].cpu().numpy())})
     ms_rep, ms_fold, ms_gat = (float(np.mean([x[i] for x in st])) for i in range(3))
     live_bytes, n_live = r.stats.bytes_out, r.stats.n_live
     # the pipeline's algorithmic HBM bytes per step: every segment byte read once by
@@ -463,10 +498,14 @@ def bench_compact_sharded(args, ctx, segs, seg_nos, seg_total, n_rec, desc, nseg
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        data, ends = step()
     torch.cuda.synchronize()
     dist.barrier()
     dt = SH.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {
+            "compact_seg_ends": ends,
+            **byte_arrays("compact_bytes", np.frombuffer(data, dtype=np.uint8))})
     res = {
         "metric": "device-resident compaction live-record rewrite GiB/s (segment bytes in)",
         "value": round(seg_total * world * args.steps / dt / 2 ** 30, 3), "unit": "GiB/s", "n_gpus": world,
@@ -528,6 +567,8 @@ def bench_etag(args, K, torch, dev, world, rank):
     if world > 1:
         from kvreplay.shard import max_over_ranks
         dt = max_over_ranks(dt)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"etag_crc": crc, "etag_summary": [len(crc), nf]})
     total = n_blob * blob
     mc = float(np.mean([a for a, _ in ms]))
     mj = float(np.mean([b for _, b in ms]))
@@ -546,6 +587,50 @@ def bench_etag(args, K, torch, dev, world, rank):
     if rank == 0:
         print(json.dumps(res))
     ctx.close()
+
+DUMP_ROWS = 1 << 19        # sampled tuples per dump: 9 float64 columns and the positions, 40 MiB
+DUMP_BYTES = 1 << 21       # sampled bytes of a byte-stream output: float64 values and positions, 32 MiB
+DUMP_SEED = 0x6B7672
+
+
+def sample_index(n, k):
+    """k of range(n), ascending: the same for every run and build (all of them when n <= k)."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def tuple_arrays(name, t):
+    """A TUPLE_DTYPE array as dump arrays: <name> = the sampled tuples, one row each, every field a
+    float64 column (all fields are below 2^53, so exact); <name>_rows = their positions;
+    <name>_sums = every field summed over the whole array, mod 2^48 (exact, and changed by a
+    difference in any tuple the sample misses, unless differences cancel)."""
+    import numpy as np
+    rows = sample_index(len(t), DUMP_ROWS)
+    s = t[rows]
+    cols = np.stack([s[f].astype(np.float64) for f in t.dtype.names], axis=1)
+    sums = [int(t[f].astype(np.uint64).sum(dtype=np.uint64)) & ((1 << 48) - 1) for f in t.dtype.names]
+    return {name: cols, name + "_rows": rows, name + "_sums": sums}
+
+
+def byte_arrays(name, b):
+    """A byte stream (uint8 array) as dump arrays: <name> = the sampled bytes, <name>_at = their
+    positions, <name>_hist = the count of every byte value over the whole stream."""
+    import numpy as np
+    at = sample_index(len(b), DUMP_BYTES)
+    return {name: b[at], name + "_at": at, name + "_hist": np.bincount(b, minlength=256)}
+
+
+def dump_outputs(dirname, rank, world, arrays):
+    """DIR/<name>.npy, float64 (every value written is an integer below 2^53); with more than one
+    rank each rank writes its own outputs as DIR/rank<r>_<name>.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, pre + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
 
 def host_cpu_info():
     """The CPU the baselines ran on: nproc, this process's affinity, the thread count used (the

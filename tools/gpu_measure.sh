@@ -22,16 +22,16 @@ for s in $STEPS; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 || { echo "smoke failed"; tail -20 "$OUT/smoke.txt"; exit 1; }
       tail -1 "$OUT/smoke.txt" ;;
     bench)
-      timeout -k 10 300 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 300 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     bench3)
-      timeout -k 10 300 python -u bench.py --config cfg3 --no-cpu --no-open > "$OUT/bench_cfg3.json" 2> "$OUT/bench_cfg3.err" || { echo "bench cfg3 failed"; tail -20 "$OUT/bench_cfg3.err"; exit 1; }
+      timeout -k 10 300 python -u bench.py --full --config cfg3 --no-cpu --no-open > "$OUT/bench_cfg3.json" 2> "$OUT/bench_cfg3.err" || { echo "bench cfg3 failed"; tail -20 "$OUT/bench_cfg3.err"; exit 1; }
       cat "$OUT/bench_cfg3.json" ;;
     bench5)
-      timeout -k 10 400 python -u bench.py --config cfg5 --no-cpu --no-open > "$OUT/bench_cfg5.json" 2> "$OUT/bench_cfg5.err" || { echo "bench cfg5 failed"; tail -20 "$OUT/bench_cfg5.err"; exit 1; }
+      timeout -k 10 400 python -u bench.py --full --config cfg5 --no-cpu --no-open > "$OUT/bench_cfg5.json" 2> "$OUT/bench_cfg5.err" || { echo "bench cfg5 failed"; tail -20 "$OUT/bench_cfg5.err"; exit 1; }
       cat "$OUT/bench_cfg5.json" ;;
     bench5c)  # cfg5 with its CPU baselines (a 4-segment sample for the faithful port, the shard for the strong one)
-      timeout -k 10 900 python -u bench.py --config cfg5 --no-open --no-stream > "$OUT/bench_cfg5_cpu.json" 2> "$OUT/bench_cfg5_cpu.err" || { echo "bench cfg5 cpu failed"; tail -20 "$OUT/bench_cfg5_cpu.err"; exit 1; }
+      timeout -k 10 900 python -u bench.py --full --config cfg5 --no-open --no-stream > "$OUT/bench_cfg5_cpu.json" 2> "$OUT/bench_cfg5_cpu.err" || { echo "bench cfg5 cpu failed"; tail -20 "$OUT/bench_cfg5_cpu.err"; exit 1; }
       cat "$OUT/bench_cfg5_cpu.json" ;;
     etag)
       timeout -k 10 300 python -u bench.py --mode etag > "$OUT/bench_etag.json" 2> "$OUT/bench_etag.err" || { echo "bench etag failed"; tail -20 "$OUT/bench_etag.err"; exit 1; }
