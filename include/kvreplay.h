@@ -416,6 +416,38 @@ int  kvr_gen_segment_device(kvr_ctx *ctx, const kvr_gen_params *p, uint64_t seg_
                             uint8_t *d_buf, uint64_t cap, uint64_t *len_out,
                             uint32_t *d_expected, uint64_t exp_cap, uint64_t *n_rec_out);
 
+/* ---- batched gets: KVStore::get for many keys against the index in HBM --------------------- */
+#define KVR_KEYS_ON_DEVICE  0x10u  /* keys and key_off are device pointers                       */
+#define KVR_GET_LOCATE_ONLY 0x20u  /* no value bytes: live_idx and val_off only; vals ignored    */
+#define KVR_GET_VERIFY      0x40u  /* re-CRC every gathered value against its tuple's crc32      */
+
+typedef struct kvr_get_stats {
+    double ms_probe, ms_gather, ms_verify;   /* device events on the context's stream */
+    uint64_t n_keys, n_found, val_bytes, n_crc_fail;
+} kvr_get_stats;
+
+/* KVStore::get (engine.rs:200-202) for n keys at once against the index of the last
+ * kvr_replay_index / kvr_ingest_index call on ctx (the segments of that call must still be where
+ * they were, as for kvr_live_keys).  Key i is keys[key_off[i] .. key_off[i+1]) — the arena format
+ * kvr_live_keys writes.  live_idx[i] = index into live[] of the key's final SET, -1 = not live
+ * (get -> None); value i is vals[val_off[i] .. val_off[i+1]) (empty for a miss: tell a miss from an
+ * empty value by live_idx); *val_bytes = val_off[n].  Duplicate keys each get their own copy.
+ * flags: KVR_KEYS_ON_DEVICE; KVR_OUT_ON_DEVICE (live_idx, val_off, vals, bad are device pointers;
+ * live_idx and val_off 8-B aligned); KVR_GET_LOCATE_ONLY; KVR_GET_VERIFY (*n_crc_fail, and
+ * bad[i] = 1 where given; not together with KVR_GET_LOCATE_ONLY).
+ * The index, the live list and the segments are only read: any number of gets may follow one
+ * index build.
+ * Returns KVR_OK; KVR_CAPACITY when vals_cap < *val_bytes (live_idx, val_off and *val_bytes are
+ * complete, nothing is written past vals + vals_cap, nothing is verified); KVR_EINVAL (no index on
+ * ctx — never built, or a later replay-type call replaced it —, key_off not non-decreasing,
+ * a key of 2^32 bytes or more, NULL where a buffer is needed); < 0 otherwise. */
+int kvr_get_batch(kvr_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, size_t n, uint32_t flags,
+                  int64_t *live_idx, uint64_t *val_off, uint8_t *vals, uint64_t vals_cap,
+                  uint64_t *val_bytes, uint8_t *bad, uint64_t *n_crc_fail);
+int kvr_last_get_stats(const kvr_ctx *ctx, kvr_get_stats *out);
+/* 0 while ctx holds no key table; otherwise a value that changes with every index build. */
+uint64_t kvr_index_epoch(const kvr_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

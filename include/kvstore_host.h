@@ -110,6 +110,25 @@ int kvs_open_ex(const char *dir, kvr_ctx *ctx, uint32_t flags, kvs_store **out, 
 int kvs_last_open_stats(const kvs_store *s, kvs_open_stats *out);
 /* KVStore::get (engine.rs:200): 1 and the value bytes if live, 0 if absent. */
 int kvs_get(const kvs_store *s, const uint8_t *key, size_t klen, const uint8_t **val, size_t *vlen);
+/* The host multi-get over a host copy of an index (live, slots: kvr_replay_index's arrays or
+ * kvr_index_build_host's) and its segments (host bytes): kvr_index_find per key, then memcpy of
+ * the values, on n_threads host threads (0 or 1: the calling thread).  Arguments, outputs and
+ * return codes as kvs_get_many, which runs this on one thread when the device cannot answer. */
+int kvh_get_many(const kvr_tuple *live, size_t n_live, const uint32_t *slots, uint64_t n_slots, const kvr_segment *segs,
+                 const uint8_t *keys, const uint64_t *key_off, size_t n, uint32_t n_threads, int64_t *live_idx,
+                 uint64_t *val_off, uint8_t *vals, uint64_t vals_cap, uint64_t *val_bytes);
+/* KVStore::get for n keys at once: key i is keys[key_off[i] .. key_off[i+1]); live_idx[i] = index
+ * of the key's final SET in the store's live list, -1 = absent; value i is
+ * vals[val_off[i] .. val_off[i+1]) (empty for a miss); *val_bytes = val_off[n].  All buffers are
+ * host memory.  When ctx still holds the key table this store's last index build left on it
+ * (kvr_index_epoch(ctx) is the value the store remembered), kvr_get_batch answers on the device;
+ * otherwise (ctx NULL, the host-fold path, or the context used for another replay since) a host
+ * loop over kvr_index_find and memcpy does.  Both give the same results.
+ * Returns KVR_OK, KVR_CAPACITY when vals_cap < *val_bytes (live_idx, val_off and *val_bytes are
+ * complete, nothing is written past vals + vals_cap), KVR_EINVAL (NULL where a buffer is needed,
+ * key_off not non-decreasing, a key of 2^32 bytes or more) or < 0. */
+int kvs_get_many(const kvs_store *s, kvr_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, size_t n,
+                 int64_t *live_idx, uint64_t *val_off, uint8_t *vals, uint64_t vals_cap, uint64_t *val_bytes);
 /* Index entry (index.rs:7 shape): segment id, value offset inside that segment file, length. */
 int kvs_locate(const kvs_store *s, const uint8_t *key, size_t klen, uint64_t *seg_id, uint64_t *val_off, uint64_t *len);
 int kvs_stats_get(const kvs_store *s, kvs_stats *out);

@@ -12,6 +12,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cerrno>
@@ -212,6 +213,15 @@ struct kvr_ctx {
     DevBuf<uint8_t> kbuf;
     uint64_t ix_live = 0, ix_slots = 0;
     bool ix_valid = false;
+    uint64_t ix_epoch = 0;                 // the key table's build number (kvr_index_epoch)
+    // batched gets (kvr_get_batch): the call's own scratch, so any number of gets may follow one
+    // index build
+    DevBuf<uint8_t> g_keys, g_vals, g_bad, g_tmp;
+    DevBuf<uint64_t> g_koff, g_vlen, g_off, g_src, g_tot, g_nch, g_cpre;
+    DevBuf<int64_t> g_idx;
+    DevBuf<uint32_t> g_exp, g_crc;
+    hipEvent_t g_ev[5] = {};
+    kvr_get_stats gstats{};
     kvr_index_stats istats{};
     DevBuf<uint8_t> ing;                   // the store's segment bytes, resident in HBM
     uint64_t ing_off = 0;
@@ -396,6 +406,10 @@ void kvr_ctx_destroy(kvr_ctx *c) {
     c->e_x.release(); c->e_cb.release(); c->e_creg.release(); c->e_out.release(); c->e_exp.release();
     c->e_cpre.release(); c->e_offs.release(); c->e_lens.release(); c->e_fail.release(); c->e_data.release();
     c->e_cdesc.release();
+    c->g_keys.release(); c->g_vals.release(); c->g_bad.release(); c->g_tmp.release(); c->g_koff.release();
+    c->g_vlen.release(); c->g_off.release(); c->g_src.release(); c->g_tot.release(); c->g_nch.release();
+    c->g_cpre.release(); c->g_idx.release(); c->g_exp.release(); c->g_crc.release();
+    for (auto &e : c->g_ev) if (e) (void)hipEventDestroy(e);
     if (c->copy) (void)hipStreamSynchronize(c->copy);
     for (int i = 0; i < 2; ++i) {
         c->slot[i].release();
@@ -1622,6 +1636,67 @@ int kvr_last_stream_stats(const kvr_ctx *c, kvr_stream_stats *out) {
 // ---------------------------------------------------------------------------------------
 // batch ETag compute / verify (kvr_etag.hip; SURVEY §8f rank 4, storage.rs:27)
 // ---------------------------------------------------------------------------------------
+// XT[t] = x^(8t) for t <= CH, XC[l] = x^(8 l CH) for l < 64, x^(8 * 64 CH), then KL (kvr_etag.hip)
+static int etag_tables(kvr_ctx *c) {
+    if (c->e_x.p) return KVR_OK;
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> x(ETAG_NX);
+    x[0] = GF_ONE;
+    for (uint32_t t = 1; t <= ETAG_CH; ++t) x[t] = gf_mul(x[t - 1], 0x00800000u);
+    uint32_t *xc = x.data() + ETAG_CH + 1;
+    xc[0] = GF_ONE;
+    for (int l = 1; l <= 64; ++l) xc[l] = gf_mul(xc[l - 1], x[ETAG_CH]);
+    // KL: per lane, nibble tables of the full-chunk lane shift x^(8 (CH - 64 (lane + 1)))
+    x.resize(ETAG_NX + ETAG_NKL);
+    for (uint32_t l = 0; l < 64; ++l)
+        for (uint32_t i = 0; i < 8; ++i)
+            for (uint32_t nb = 0; nb < 16; ++nb)
+                x[ETAG_NX + l * 128 + i * 16 + nb] = gf_mul(nb << (4 * i), x[ETAG_CH - 64 * (l + 1)]);
+    if (c->e_x.ensure(x.size())) return KVR_ENOMEM;
+    HIPCHK(hipMemcpyAsync(c->e_x.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));   // x is a local
+    return KVR_OK;
+}
+
+// The device part of a batch over arrays that are all in HBM: blob v = d_data[d_offs[v] ..
+// + d_lens[v]) owns chunks [d_cpre[v], d_cpre[v + 1]) of nch; d_exp may be NULL.  Queues the chunk
+// map, the byte pass and the join on the context's stream (ev[0..2] around them), CRCs to d_out,
+// mismatches counted in e_fail; the caller synchronises.  kvr_etag_batch and kvr_get_batch's
+// verify-on-read end here.
+static int etag_launch(kvr_ctx *c, const uint8_t *d_data, uint64_t data_len, const uint64_t *d_offs,
+                       const uint64_t *d_lens, const uint64_t *d_cpre, size_t n, uint64_t nch, const uint32_t *d_exp,
+                       uint32_t *d_out) {
+    hipStream_t st = c->stream;
+    const int rc = etag_tables(c);
+    if (rc != KVR_OK) return rc;
+    if (c->e_cdesc.ensure(nch + 1) || c->e_creg.ensure(nch) || c->e_fail.ensure(1)) return KVR_ENOMEM;
+    HIPCHK(hipMemsetAsync(c->e_fail.p, 0, 8, st));
+    const uint32_t mgrid = (uint32_t)std::min<uint64_t>((nch + 255) / 256, 65536);
+    if (nch)
+        hipLaunchKernelGGL(k_etag_map, dim3(mgrid), dim3(256), 0, st, d_cpre, (uint64_t)n, d_offs, d_lens, nch,
+                           c->e_cdesc.p);
+    HIPCHK(hipEventRecord(c->ev[0], st));
+    if (nch) {
+        const uint64_t per = (uint64_t)ETAG_WPB * (KVR_ETAG_DB ? ETAG_NC_DB : ETAG_NC);
+        if (!c->e_wg_per_cu) {   // persistent grid: exactly the resident workgroups
+            int occ = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_etag_chunk, 64 * ETAG_WPB, 0) != hipSuccess || occ < 1)
+                occ = 1;
+            c->e_wg_per_cu = (uint32_t)occ;
+        }
+        const uint64_t g = std::min<uint64_t>((nch + per - 1) / per, (uint64_t)c->n_cu * c->e_wg_per_cu);
+        hipLaunchKernelGGL(k_etag_chunk, dim3((uint32_t)g), dim3(64 * ETAG_WPB), 0, st, d_data, data_len, c->e_cdesc.p,
+                           nch, c->crc.p, c->e_x.p, c->e_creg.p);
+    }
+    HIPCHK(hipEventRecord(c->ev[1], st));
+    hipLaunchKernelGGL(k_etag_join, dim3((uint32_t)((n + ETAG_WPB - 1) / ETAG_WPB)), dim3(64 * ETAG_WPB), 0, st,
+                       d_lens, d_cpre, (uint64_t)n, c->e_creg.p, c->e_x.p, d_exp, d_out,
+                       reinterpret_cast<unsigned long long *>(c->e_fail.p));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[2], st));
+    return KVR_OK;
+}
+
 extern "C" {
 
 int kvr_etag_batch(kvr_ctx *c, const uint8_t *data, uint64_t data_len, const uint64_t *offs, const uint64_t *lens,
@@ -1644,36 +1719,18 @@ int kvr_etag_batch(kvr_ctx *c, const uint8_t *data, uint64_t data_len, const uin
     if (nch >= 0xFFFFFFFFull || data_len >= (1ull << 48)) return KVR_EINVAL;   // (k_etag_map's packed descriptors)
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    if (!c->e_x.p) {   // XT[t] = x^(8t) for t <= CH, XC[l] = x^(8 l CH) for l < 64, x^(8 * 64 CH)
-        std::vector<uint32_t> x(ETAG_NX);
-        x[0] = GF_ONE;
-        for (uint32_t t = 1; t <= ETAG_CH; ++t) x[t] = gf_mul(x[t - 1], 0x00800000u);
-        uint32_t *xc = x.data() + ETAG_CH + 1;
-        xc[0] = GF_ONE;
-        for (int l = 1; l <= 64; ++l) xc[l] = gf_mul(xc[l - 1], x[ETAG_CH]);
-        // KL: per lane, nibble tables of the full-chunk lane shift x^(8 (CH - 64 (lane + 1)))
-        x.resize(ETAG_NX + ETAG_NKL);
-        for (uint32_t l = 0; l < 64; ++l)
-            for (uint32_t i = 0; i < 8; ++i)
-                for (uint32_t nb = 0; nb < 16; ++nb)
-                    x[ETAG_NX + l * 128 + i * 16 + nb] = gf_mul(nb << (4 * i), x[ETAG_CH - 64 * (l + 1)]);
-        if (c->e_x.ensure(x.size())) return KVR_ENOMEM;
-        HIPCHK(hipMemcpyAsync(c->e_x.p, x.data(), x.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));   // x is a local
-    }
+    int rc = etag_tables(c);
+    if (rc != KVR_OK) return rc;
     const uint8_t *d_data = data;
     if (!(flags & KVR_SEGS_ON_DEVICE)) {
         if (c->e_data.ensure(data_len + 256)) return KVR_ENOMEM;
         if (data_len) HIPCHK(hipMemcpyAsync(c->e_data.p, data, data_len, hipMemcpyHostToDevice, st));
         d_data = c->e_data.p;
     }
-    if (c->e_cpre.ensure(n + 1) || c->e_offs.ensure(n) || c->e_lens.ensure(n) || c->e_cdesc.ensure(nch + 1) ||
-        c->e_creg.ensure(nch) || c->e_fail.ensure(1))
-        return KVR_ENOMEM;
+    if (c->e_cpre.ensure(n + 1) || c->e_offs.ensure(n) || c->e_lens.ensure(n)) return KVR_ENOMEM;
     HIPCHK(hipMemcpyAsync(c->e_cpre.p, cpre.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->e_offs.p, offs, n * 8, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(c->e_lens.p, lens, n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(c->e_fail.p, 0, 8, st));
     uint32_t *d_out = crc_out;
     if (!(flags & KVR_OUT_ON_DEVICE)) {
         if (c->e_out.ensure(n)) return KVR_ENOMEM;
@@ -1685,29 +1742,8 @@ int kvr_etag_batch(kvr_ctx *c, const uint8_t *data, uint64_t data_len, const uin
         HIPCHK(hipMemcpyAsync(c->e_exp.p, expected, n * 4, hipMemcpyHostToDevice, st));
         d_exp = c->e_exp.p;
     }
-    const uint32_t mgrid = (uint32_t)std::min<uint64_t>((nch + 255) / 256, 65536);
-    if (nch)
-        hipLaunchKernelGGL(k_etag_map, dim3(mgrid), dim3(256), 0, st, c->e_cpre.p, (uint64_t)n, c->e_offs.p, c->e_lens.p,
-                           nch, c->e_cdesc.p);
-    HIPCHK(hipEventRecord(c->ev[0], st));
-    if (nch) {
-        const uint64_t per = (uint64_t)ETAG_WPB * (KVR_ETAG_DB ? ETAG_NC_DB : ETAG_NC);
-        if (!c->e_wg_per_cu) {   // persistent grid: exactly the resident workgroups
-            int occ = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_etag_chunk, 64 * ETAG_WPB, 0) != hipSuccess || occ < 1)
-                occ = 1;
-            c->e_wg_per_cu = (uint32_t)occ;
-        }
-        const uint64_t g = std::min<uint64_t>((nch + per - 1) / per, (uint64_t)c->n_cu * c->e_wg_per_cu);
-        hipLaunchKernelGGL(k_etag_chunk, dim3((uint32_t)g), dim3(64 * ETAG_WPB), 0, st, d_data, data_len, c->e_cdesc.p,
-                           nch, c->crc.p, c->e_x.p, c->e_creg.p);
-    }
-    HIPCHK(hipEventRecord(c->ev[1], st));
-    hipLaunchKernelGGL(k_etag_join, dim3((uint32_t)((n + ETAG_WPB - 1) / ETAG_WPB)), dim3(64 * ETAG_WPB), 0, st,
-                       c->e_lens.p, c->e_cpre.p, (uint64_t)n, c->e_creg.p, c->e_x.p, d_exp, d_out,
-                       reinterpret_cast<unsigned long long *>(c->e_fail.p));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev[2], st));
+    rc = etag_launch(c, d_data, data_len, c->e_offs.p, c->e_lens.p, c->e_cpre.p, n, nch, d_exp, d_out);
+    if (rc != KVR_OK) return rc;
     uint64_t fails = 0;
     HIPCHK(hipMemcpyAsync(&fails, c->e_fail.p, 8, hipMemcpyDeviceToHost, st));
     if (!(flags & KVR_OUT_ON_DEVICE)) HIPCHK(hipMemcpyAsync(crc_out, d_out, n * 4, hipMemcpyDeviceToHost, st));
@@ -1738,4 +1774,5 @@ void kvr_etag_format(uint32_t crc, char *out) {
 }  // extern "C"
 
 #include "kvr_index.hip"
+#include "kvr_get.hip"
 #include "kvr_multi.hip"

@@ -92,6 +92,8 @@ struct kvs_store {
     // (kvr_replay_index / kvr_index_find)
     std::vector<kvr_tuple> live;
     std::vector<uint32_t> slots;
+    uint64_t epoch = 0;                          // kvr_index_epoch of the context after the device built
+                                                 // this index; 0: built on the host (kvs_get_many)
     uint64_t total_bytes = 0;
     uint64_t active_id = 0;
     uint32_t open_flags = 0;
@@ -322,6 +324,7 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 // -> the same table on the host
 int index_host_fold(kvs_store *s, kvr_ctx *ctx, uint32_t stream_flags, kvr_error *err) {
     const size_t n = s->segs.size();
+    s->epoch = 0;   // the table is built here: the context holds none for this store
     uint64_t total = 0;
     for (const kvr_segment &g : s->segs) total += g.len;
     if (!ctx && total) return KVR_EINVAL;   // records to replay, and no device to replay them on
@@ -363,6 +366,7 @@ int index_device(kvs_store *s, kvr_ctx *ctx, F call) {
     if (rc != KVR_OK) return rc;
     s->live.resize(nl);
     s->slots.resize(ns);
+    s->epoch = kvr_index_epoch(ctx);   // this index is the one in the context's HBM (kvs_get_many)
     return KVR_OK;
 }
 
@@ -739,6 +743,71 @@ int kvs_get(const kvs_store *s, const uint8_t *key, size_t klen, const uint8_t *
     if (val) *val = s->segs[t.seg_idx].bytes + t.rec_off + 9 + t.key_len;
     if (vlen) *vlen = t.val_len;
     return 1;
+}
+
+int kvh_get_many(const kvr_tuple *live, size_t n_live, const uint32_t *slots, uint64_t n_slots, const kvr_segment *segs,
+                 const uint8_t *keys, const uint64_t *key_off, size_t n, uint32_t n_threads, int64_t *live_idx,
+                 uint64_t *val_off, uint8_t *vals, uint64_t vals_cap, uint64_t *val_bytes) {
+    if (!val_bytes) return KVR_EINVAL;
+    *val_bytes = 0;
+    if (n == 0) {
+        if (val_off) val_off[0] = 0;
+        return KVR_OK;
+    }
+    if (!key_off || !live_idx || !val_off || (vals_cap && !vals) || (n_live && (!live || !slots || !segs))) return KVR_EINVAL;
+    for (size_t i = 0; i < n; ++i)
+        if (key_off[i + 1] < key_off[i] || key_off[i + 1] - key_off[i] >= (1ull << 32)) return KVR_EINVAL;
+    if (key_off[n] && !keys) return KVR_EINVAL;
+    // keys [i0, i1) per thread: the lookups, then (offsets known) the copies
+    const size_t nth = std::max<size_t>(1, std::min<size_t>(n_threads, n));
+    auto run = [&](auto body) {
+        std::vector<std::thread> th;
+        for (size_t t = 1; t < nth; ++t) th.emplace_back(body, n * t / nth, n * (t + 1) / nth);
+        body((size_t)0, n / nth);
+        for (auto &x : th) x.join();
+    };
+    run([&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; ++i) {
+            const size_t klen = (size_t)(key_off[i + 1] - key_off[i]);
+            live_idx[i] = n_live ? kvr_index_find(live, slots, n_slots, segs, klen ? keys + key_off[i] : nullptr, klen) : -1;
+        }
+    });
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {
+        val_off[i] = total;
+        if (live_idx[i] >= 0) total += live[(size_t)live_idx[i]].val_len;
+    }
+    val_off[n] = total;
+    *val_bytes = total;
+    if (total > vals_cap) return KVR_CAPACITY;
+    run([&](size_t i0, size_t i1) {
+        for (size_t i = i0; i < i1; ++i) {
+            if (live_idx[i] < 0) continue;
+            const kvr_tuple &t = live[(size_t)live_idx[i]];
+            if (t.val_len) memcpy(vals + val_off[i], segs[t.seg_idx].bytes + t.rec_off + 9 + t.key_len, t.val_len);
+        }
+    });
+    return KVR_OK;
+}
+
+int kvs_get_many(const kvs_store *s, kvr_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, size_t n,
+                 int64_t *live_idx, uint64_t *val_off, uint8_t *vals, uint64_t vals_cap, uint64_t *val_bytes) {
+    if (!s || !val_bytes) return KVR_EINVAL;
+    *val_bytes = 0;
+    if (n == 0) {
+        if (val_off) val_off[0] = 0;
+        return KVR_OK;
+    }
+    if (!key_off || !live_idx || !val_off || (vals_cap && !vals)) return KVR_EINVAL;
+    for (size_t i = 0; i < n; ++i)
+        if (key_off[i + 1] < key_off[i] || key_off[i + 1] - key_off[i] >= (1ull << 32)) return KVR_EINVAL;
+    if (key_off[n] && !keys) return KVR_EINVAL;
+    // the device answers while the context still holds this store's key table
+    if (ctx && s->epoch && kvr_index_epoch(ctx) == s->epoch)
+        return kvr_get_batch(ctx, keys, key_off, n, 0, live_idx, val_off, vals, vals_cap, val_bytes, nullptr, nullptr);
+    // the host loop: KVStore::get per key over the host copy of the index and the segments
+    return kvh_get_many(s->live.data(), s->live.size(), s->slots.data(), s->slots.size(), s->segs.data(), keys, key_off, n,
+                        1, live_idx, val_off, vals, vals_cap, val_bytes);
 }
 
 int kvs_locate(const kvs_store *s, const uint8_t *key, size_t klen, uint64_t *seg_id, uint64_t *val_off, uint64_t *len) {

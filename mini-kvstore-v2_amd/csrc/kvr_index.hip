@@ -20,6 +20,7 @@ namespace {
 __host__ __device__ __forceinline__ uint32_t ix_hash(uint32_t h) { return ht_mix(h); }
 
 constexpr uint32_t IX_DEAD = 0xFFFFFFFFu;   // a key whose last record is a DEL: probe on
+std::atomic<uint64_t> index_epochs{0};      // key tables built so far, over all contexts
 
 // slots[h] from fold entry h: free -> 0, a live key -> 1 + its position in the live list, a
 // deleted key -> IX_DEAD (keeps the probe sequences of the keys behind it intact).  No atomics:
@@ -192,6 +193,7 @@ int kvr_replay_index(kvr_ctx *c, const kvr_segment *segs, size_t n, uint32_t fla
     c->ix_live = total;
     c->ix_slots = ns;
     c->ix_valid = true;
+    c->ix_epoch = ++index_epochs;   // kvr_index_epoch: no other build in this process has this value
     c->istats.n_live = total;
     c->istats.n_slots = ns;
     c->istats.fold_rounds = c->fold_rounds;

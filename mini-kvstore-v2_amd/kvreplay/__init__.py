@@ -27,6 +27,7 @@ EINVAL, EHIP, EIO, ENOMEM = -1, -2, -3, -4
 E_NONE, E_OPEN, E_KEY_LEN, E_KEY, E_UTF8, E_VAL_LEN, E_VAL, E_OPCODE = range(8)
 KIND_NAMES = {0: "NONE", 1: "OPEN", 2: "KEY_LEN", 3: "KEY", 4: "UTF8", 5: "VAL_LEN", 6: "VAL", 7: "OPCODE"}
 SEGS_ON_DEVICE, OUT_ON_DEVICE, EXPECTED_ON_DEVICE, HOST_PINNED = 0x1, 0x2, 0x4, 0x8
+KEYS_ON_DEVICE, GET_LOCATE_ONLY, GET_VERIFY = 0x10, 0x20, 0x40
 TF_VERIFIED, TF_CRC_FAIL = 0x1, 0x2
 
 TUPLE_DTYPE = np.dtype([("rec_off", "<u8"), ("seg_idx", "<u4"), ("key_len", "<u4"), ("val_len", "<u4"),
@@ -64,6 +65,12 @@ class MultiStats(C.Structure):
 class EtagStats(C.Structure):
     _fields_ = [("ms_chunk", C.c_double), ("ms_join", C.c_double), ("bytes", C.c_uint64),
                 ("n_blobs", C.c_uint64), ("n_chunks", C.c_uint64), ("n_fail", C.c_uint64)]
+
+
+class GetStats(C.Structure):
+    _fields_ = [("ms_probe", C.c_double), ("ms_gather", C.c_double), ("ms_verify", C.c_double),
+                ("n_keys", C.c_uint64), ("n_found", C.c_uint64), ("val_bytes", C.c_uint64),
+                ("n_crc_fail", C.c_uint64)]
 
 
 class GenParams(C.Structure):
@@ -155,6 +162,10 @@ def _load():
     rep.kvr_index_fetch.argtypes = [P, U32, P, SZ, P, U64]
     rep.kvr_live_keys.argtypes = [P, U32, P, U64, P, SZ, C.POINTER(U64)]
     rep.kvr_last_index_stats.argtypes = [P, C.POINTER(IndexStats)]
+    rep.kvr_get_batch.argtypes = [P, P, P, SZ, U32, P, P, P, U64, C.POINTER(U64), P, C.POINTER(U64)]
+    rep.kvr_last_get_stats.argtypes = [P, C.POINTER(GetStats)]
+    rep.kvr_index_epoch.argtypes = [P]
+    rep.kvr_index_epoch.restype = U64
     rep.kvr_index_slots.argtypes = [U64]
     rep.kvr_index_slots.restype = U64
     rep.kvr_index_hash.argtypes = [U32]
@@ -200,6 +211,8 @@ def _load():
     host.kvs_open_ex.argtypes = [C.c_char_p, P, U32, C.POINTER(P), C.POINTER(Error), C.c_char_p, SZ]
     host.kvs_last_open_stats.argtypes = [P, C.POINTER(OpenStats)]
     host.kvs_get.argtypes = [P, P, SZ, C.POINTER(P), C.POINTER(SZ)]
+    host.kvs_get_many.argtypes = [P, P, P, P, SZ, P, P, P, U64, C.POINTER(U64)]
+    host.kvh_get_many.argtypes = [P, SZ, P, U64, C.POINTER(Segment), P, P, SZ, U32, P, P, P, U64, C.POINTER(U64)]
     host.kvs_locate.argtypes = [P, P, SZ, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]
     host.kvs_stats_get.argtypes = [P, C.POINTER(StoreStats)]
     host.kvs_num_keys.argtypes = [P]
@@ -343,6 +356,38 @@ class ReplayResult:
     n: int
     error: Error | None
     stats: Stats
+
+
+def key_arena(keys):
+    """A list of bytes / str keys -> (packed key bytes uint8 array, offsets: n + 1 uint64): the
+    arena format of kvr_live_keys, which kvr_get_batch reads."""
+    kb = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+    offs = np.zeros(len(kb) + 1, dtype=np.uint64)
+    if kb:
+        offs[1:] = np.cumsum([len(k) for k in kb], dtype=np.uint64)
+    return np.frombuffer(b"".join(kb), dtype=np.uint8), offs
+
+
+@dataclass
+class GetResult:
+    """kvr_get_batch's answer.  live_idx / val_off / values / bad are numpy arrays, or None where
+    the output stayed in device memory (out_ptrs) or was not asked for."""
+    status: int
+    live_idx: np.ndarray | None
+    val_off: np.ndarray | None
+    values: np.ndarray | None
+    n_crc_fail: int
+    bad: np.ndarray | None
+    stats: GetStats
+    val_bytes: int = 0
+
+    def value(self, i):
+        """KVStore::get's answer for key i: its value bytes, None when the key is not live."""
+        if self.live_idx[i] < 0:
+            return None
+        if self.values is None:
+            raise ValueError("no value bytes were gathered (values=False or device outputs)")
+        return self.values[int(self.val_off[i]): int(self.val_off[i + 1])].tobytes()
 
 
 class CompactResult:
@@ -694,6 +739,62 @@ class Context:
             raise NativeError(f"kvr_live_keys: {rc}")
         return keys[: kb.value], offs
 
+    def index_epoch(self) -> int:
+        """kvr_index_epoch: 0 while the context holds no key table, else the table's build number."""
+        return int(self._rep.kvr_index_epoch(self.h))
+
+    def last_get_stats(self) -> GetStats:
+        s = GetStats()
+        self._rep.kvr_last_get_stats(self.h, C.byref(s))
+        return s
+
+    def get_batch(self, keys, values=True, verify=False, keys_ptr=None, out_ptrs=None, vals_cap=None):
+        """KVStore::get for many keys at once against the index the last replay_index / ingest_index
+        left on the device (kvr_get_batch).  keys: a list of bytes / str, or an (arena, offsets) pair
+        as live_keys returns; or keys_ptr = (device keys pointer, device offsets pointer, n) with the
+        keys already in HBM.  values=False locates only (live_idx and val_off); verify=True re-CRCs
+        every gathered value against its tuple (n_crc_fail, bad).  out_ptrs = (live_idx, val_off, vals,
+        vals_cap, bad or None) device pointers keeps every output in HBM (the arrays of the result
+        are then None, and KVR_CAPACITY is returned as the status).  Host outputs retry once on
+        KVR_CAPACITY with the size the first call reported.  Returns GetResult."""
+        flags = (0 if values else GET_LOCATE_ONLY) | (GET_VERIFY if verify else 0)
+        if keys_ptr is not None:
+            kp, op, n = keys_ptr
+            flags |= KEYS_ON_DEVICE
+            keep = None
+        else:
+            arena, offs = keys if isinstance(keys, tuple) else key_arena(keys)
+            arena = np.ascontiguousarray(arena, dtype=np.uint8)
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            n = len(offs) - 1
+            kp, op = (arena.ctypes.data if arena.size else None), offs.ctypes.data
+            keep = (arena, offs)
+        vb, nf = C.c_uint64(), C.c_uint64()
+        if out_ptrs is not None:
+            ip, vop, vp, cap, bp = out_ptrs
+            rc = self._rep.kvr_get_batch(self.h, kp, op, n, flags | OUT_ON_DEVICE, ip, vop, vp, cap, C.byref(vb), bp,
+                                         C.byref(nf))
+            if rc < 0:
+                raise NativeError(f"kvr_get_batch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+            return GetResult(rc, None, None, None, int(nf.value), None, self.last_get_stats(), int(vb.value))
+        idx = np.zeros(max(n, 1), dtype=np.int64)
+        voff = np.zeros(n + 1, dtype=np.uint64)
+        bad = np.zeros(max(n, 1), dtype=np.uint8) if verify else None
+        cap = 0 if not values else vals_cap if vals_cap is not None else max(4096, 64 * n)
+        for _ in range(2):
+            vals = np.zeros(max(cap, 1), dtype=np.uint8) if values else None
+            rc = self._rep.kvr_get_batch(self.h, kp, op, n, flags, idx.ctypes.data, voff.ctypes.data,
+                                         vals.ctypes.data if values else None, cap, C.byref(vb),
+                                         bad.ctypes.data if verify else None, C.byref(nf))
+            if rc != CAPACITY or vals_cap is not None:
+                break
+            cap = int(vb.value)
+        if rc < 0:
+            raise NativeError(f"kvr_get_batch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        del keep
+        return GetResult(rc, idx[:n], voff, vals[: vb.value] if values and rc == OK else None, int(nf.value),
+                         bad[:n] if verify else None, self.last_get_stats(), int(vb.value))
+
     def etag_batch(self, data, offs, lens, expected=None, on_device=False, data_len=None):
         """Batch ETag (kvr_etag_batch): CRC-32 of data[offs[i]:offs[i]+lens[i]] for every i.
         data is bytes / a uint8 array, or a device pointer with on_device=True (then data_len).
@@ -865,6 +966,38 @@ def index_build_host(live):
     return slots
 
 
+def host_get_many(index, keys, threads=1, segments=None, vals_cap=None):
+    """kvh_get_many: the host multi-get (kvr_index_find + memcpy per key, on threads host threads)
+    over an Index and its host segments.  keys as Context.get_batch takes them.  Returns GetResult
+    (stats None)."""
+    _, host = _load()
+    segs = segments if segments is not None else index._segs
+    arrs = [np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else np.ascontiguousarray(s)
+            for s in segs]
+    cs = (Segment * max(len(arrs), 1))(*[Segment(i, a.ctypes.data if a.size else None, a.size)
+                                         for i, a in enumerate(arrs)])
+    arena, offs = keys if isinstance(keys, tuple) else key_arena(keys)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = len(offs) - 1
+    idx = np.zeros(max(n, 1), dtype=np.int64)
+    voff = np.zeros(n + 1, dtype=np.uint64)
+    vb = C.c_uint64()
+    cap = vals_cap if vals_cap is not None else max(4096, 64 * n)
+    for _ in range(2):
+        vals = np.empty(max(cap, 1), dtype=np.uint8)
+        rc = host.kvh_get_many(index.live.ctypes.data if len(index.live) else None, len(index.live),
+                               index.slots.ctypes.data, len(index.slots), cs, arena.ctypes.data if arena.size else None,
+                               offs.ctypes.data, n, threads, idx.ctypes.data, voff.ctypes.data, vals.ctypes.data, cap,
+                               C.byref(vb))
+        if rc != CAPACITY or vals_cap is not None:
+            break
+        cap = int(vb.value)
+    if rc < 0:
+        raise NativeError(f"kvh_get_many: {rc}")
+    return GetResult(rc, idx[:n], voff, vals[: vb.value] if rc == OK else None, 0, None, None, int(vb.value))
+
+
 def index_hash(tag):
     rep, _ = _load()
     return int(rep.kvr_index_hash(tag))
@@ -902,6 +1035,28 @@ class KVStore:
         if not found:
             return None
         return C.string_at(vp.value, vl.value) if vl.value else b""
+
+    def get_many(self, keys, device=True):
+        """get for a list of keys at once (kvs_get_many) -> a list of bytes | None.  device=True
+        lets the store answer on the GPU while its context still holds the store's key table;
+        otherwise, and with device=False, the host loop answers.  Same results either way."""
+        arena, offs = key_arena(keys)
+        n = len(offs) - 1
+        ctx = self._ctx.h if device and self._ctx is not None else None
+        idx = np.zeros(max(n, 1), dtype=np.int64)
+        voff = np.zeros(n + 1, dtype=np.uint64)
+        vb = C.c_uint64()
+        cap = max(4096, 64 * n)
+        for _ in range(2):
+            vals = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self._host.kvs_get_many(self._h, ctx, arena.ctypes.data if arena.size else None, offs.ctypes.data, n,
+                                         idx.ctypes.data, voff.ctypes.data, vals.ctypes.data, cap, C.byref(vb))
+            if rc != CAPACITY:
+                break
+            cap = int(vb.value)
+        if rc != OK:
+            raise NativeError(f"kvs_get_many: {rc}")
+        return [vals[int(voff[i]): int(voff[i + 1])].tobytes() if idx[i] >= 0 else None for i in range(n)]
 
     def locate(self, key):
         kb = key.encode() if isinstance(key, str) else bytes(key)
