@@ -207,6 +207,22 @@ int      kvr_index_build_host(const kvr_tuple *live, size_t n_live, uint32_t *sl
 int  kvr_live_keys(kvr_ctx *ctx, uint32_t flags, uint8_t *keys, uint64_t keys_cap, uint64_t *key_off,
                    size_t off_cap, uint64_t *key_bytes);
 
+/* The fold's side inputs (test and diagnostic access; tests/test_fold_paths.py compares them with
+ * the oracle on every replay path).  The last-writer fold does not compare keys in the segment
+ * bytes: the replay pipeline writes, beside every tuple, the key's first min(key_len, 16) bytes
+ * zero padded to 16 (the whole comparison for keys of at most 16 bytes) and the pair (key_tag,
+ * key_len), and the fold reads those.  kvr_fold_keys_fetch copies them to host memory for the
+ * tuples of the last folding call on ctx, in tuple order (all records, not only the live ones):
+ * prefix16 receives 16 bytes per tuple, tag_len two words per tuple (key_tag, then key_len),
+ * *n = the tuple count.  They survive every entry point that folds -- kvr_replay_live,
+ * kvr_replay_last, kvr_replay_index, kvr_ingest_index, kvr_compact, kvr_compact_stage (and
+ * _export / _finish after it) -- and kvr_replay, kvr_live_keys, kvr_index_fetch and kvr_get_batch
+ * calls after it, until the next folding call.  It launches no kernel and changes no state.
+ * Returns KVR_OK; KVR_CAPACITY (*n set) when cap < *n; KVR_EINVAL when no folding call has run on
+ * ctx, when the last one failed or had no segments, or when it kept no prefixes (a replay batched
+ * past the pool-slot limit whose output outgrew its first buffer folds on the segment bytes). */
+int  kvr_fold_keys_fetch(kvr_ctx *ctx, uint8_t *prefix16, uint32_t *tag_len, size_t cap, size_t *n);
+
 /* ---- ingest: the store's files into HBM while they are being read -------------------------
  * kvr_ingest_begin reserves HBM for total_bytes of segments (KVR_ENOMEM when they do not fit:
  * replay them batch-wise with kvr_replay_stream instead).  kvr_ingest_push queues the copy of one

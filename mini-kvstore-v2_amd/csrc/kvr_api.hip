@@ -952,10 +952,10 @@ static int compact_front(kvr_ctx *c, const kvr_segment *segs, size_t n, uint32_t
     uint64_t bytes_in = 0;
     for (size_t i = 0; i < n; ++i) bytes_in += segs[i].len;
     cs->bytes_in = bytes_in;
+    c->ckeys_ok = false;
     if (n == 0) return KVR_OK;
     // 1. replay into context-resident tuples; the segment bytes stay in HBM (c->segs)
     size_t nt = 0;
-    c->ckeys_ok = false;
     if (c->ctup.ensure(bytes_in / 64 + 1024) || c->ckeys.ensure(c->ctup.n) || c->ctk.ensure(c->ckeys.n)) return KVR_ENOMEM;
     const uint32_t rflags = (flags & KVR_SEGS_ON_DEVICE) | KVR_OUT_ON_DEVICE;
     c->kout = c->ckeys.p;   // the tuples' key prefixes alongside them (k_fold_claim / k_fold_verify)
@@ -965,7 +965,7 @@ static int compact_front(kvr_ctx *c, const kvr_segment *segs, size_t n, uint32_t
         c->kout = c->ckeys.p;
         rc = kvr_replay(c, segs, n, rflags, nullptr, 0, c->ctup.p, c->ctup.n, &nt, err);
     }
-    c->ckeys_ok = c->kout != nullptr;   // (a batched replay past the output capacity drops them)
+    c->ckeys_ok = rc == KVR_OK && c->kout != nullptr;   // (a batched replay past the output capacity drops them)
     c->kout = nullptr;
     if (rc != KVR_OK) return rc;
     cs->ms_replay = c->stats.ms_total;
@@ -1400,6 +1400,24 @@ int kvr_compact_finish(kvr_ctx *c, const uint8_t *d_win, uint32_t flags, uint64_
 int kvr_last_compact_stats(const kvr_ctx *c, kvr_compact_stats *out) {
     if (!c || !out) return KVR_EINVAL;
     *out = c->cstats;
+    return KVR_OK;
+}
+
+// the fold's side inputs of the last folding call (compact_front), copied out; nothing else reads
+// or writes ckeys / ctk between two folding calls, so they outlive every entry point built on it
+int kvr_fold_keys_fetch(kvr_ctx *c, uint8_t *prefix16, uint32_t *tag_len, size_t cap, size_t *n) {
+    if (!c || !n) return KVR_EINVAL;
+    *n = 0;
+    const size_t nt = c->c_nt;
+    if (!c->ckeys_ok || c->ckeys.n < nt || c->ctk.n < nt) return KVR_EINVAL;
+    *n = nt;
+    if (nt > cap) return KVR_CAPACITY;
+    if (nt == 0) return KVR_OK;
+    if (!prefix16 || !tag_len) return KVR_EINVAL;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(prefix16, c->ckeys.p, nt * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tag_len, c->ctk.p, nt * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return KVR_OK;
 }
 

@@ -162,6 +162,7 @@ def _load():
     rep.kvr_index_fetch.argtypes = [P, U32, P, SZ, P, U64]
     rep.kvr_live_keys.argtypes = [P, U32, P, U64, P, SZ, C.POINTER(U64)]
     rep.kvr_last_index_stats.argtypes = [P, C.POINTER(IndexStats)]
+    rep.kvr_fold_keys_fetch.argtypes = [P, P, P, SZ, C.POINTER(SZ)]
     rep.kvr_get_batch.argtypes = [P, P, P, SZ, U32, P, P, P, U64, C.POINTER(U64), P, C.POINTER(U64)]
     rep.kvr_last_get_stats.argtypes = [P, C.POINTER(GetStats)]
     rep.kvr_index_epoch.argtypes = [P]
@@ -649,6 +650,40 @@ class Context:
             raise NativeError(f"kvr_replay_live: {self._rep.kvr_strerror(rc).decode()} ({rc})")
         tuples = out_arr[: n_out.value] if out_arr is not None and rc == OK else None
         return ReplayResult(rc, tuples, n_out.value, err if rc == CORRUPTED else None, self.last_stats())
+
+    def replay_last(self, segments, seg_ids=None, on_device=False, cap=None):
+        """Replay + fold with every key's last record kept, a DEL included (kvr_replay_last), in
+        (segment, offset) order.  Returns ReplayResult."""
+        segs, keep, total = self._segments(segments, seg_ids, on_device)
+        if cap is None:
+            cap = max(1024, total // 24 + len(segments))
+        out_arr = np.zeros(max(cap, 1), dtype=TUPLE_DTYPE)
+        n_out = C.c_size_t()
+        err = Error()
+        rc = self._rep.kvr_replay_last(self.h, segs, len(segments), SEGS_ON_DEVICE if on_device else 0,
+                                       out_arr.ctypes.data, cap, C.byref(n_out), C.byref(err))
+        if rc == CAPACITY:
+            return self.replay_last(segments, seg_ids, on_device, n_out.value + 16)
+        if rc < 0:
+            raise NativeError(f"kvr_replay_last: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        tuples = out_arr[: n_out.value] if rc == OK else None
+        return ReplayResult(rc, tuples, n_out.value, err if rc == CORRUPTED else None, self.last_stats())
+
+    def fold_keys(self):
+        """The fold's side inputs of the last folding call (kvr_fold_keys_fetch), one row per
+        replayed tuple -> (prefixes: n x 16 uint8, tag_len: n x 2 uint32 of (key_tag, key_len)).
+        Raises NativeError with the code (KVR_EINVAL: that call kept none, or none has run)."""
+        n = C.c_size_t()
+        rc = self._rep.kvr_fold_keys_fetch(self.h, None, None, 0, C.byref(n))
+        if rc not in (OK, CAPACITY):
+            raise NativeError(f"kvr_fold_keys_fetch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        pre = np.zeros((n.value, 16), dtype=np.uint8)
+        tl = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            rc = self._rep.kvr_fold_keys_fetch(self.h, pre.ctypes.data, tl.ctypes.data, n.value, C.byref(n))
+            if rc != OK:
+                raise NativeError(f"kvr_fold_keys_fetch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        return pre, tl
 
     def replay_index(self, segments, seg_ids=None, on_device=False):
         """Replay + fold + key table on the device (kvr_replay_index) -> Index (live tuples in

@@ -78,12 +78,12 @@ def edge():
     return segs, want, d, keys
 
 
-def dev_place(segs, base_off):
+def dev_place(segs, base_off, fill=0):
     """The segments in one torch buffer, segment i at an address = base_off (mod 256), as
-    test_piece_mode._dev_place does."""
+    test_piece_mode._dev_place does; every byte outside a segment is fill."""
     torch = pytest.importorskip("torch")
     tot = sum((len(s) + 511) & ~255 for s in segs) + 512
-    buf = torch.zeros(tot, dtype=torch.uint8, device="cuda")
+    buf = torch.full((tot,), fill, dtype=torch.uint8, device="cuda")
     ptrs, off, offs = [], base_off, []
     for s in segs:
         buf[off: off + len(s)] = torch.from_numpy(np.frombuffer(s, dtype=np.uint8).copy()).cuda()

@@ -146,8 +146,9 @@ def test_tile_boundary_sweep(gctx):
             assert rg.status == 0 and np.array_equal(rg.tuples, ref), (shift, tps)
 
 
-def test_adversarial_speculation(gctx):
-    """Values that look like records defeat the speculative entry; results must stay exact."""
+def adversarial_store():
+    """(seg, inner, zeros): a segment whose values are record chains (inner), runs of zeros (9-byte
+    empty SETs) and random bytes, cut at random lengths, with DELs between them."""
     inner = b"".join(rec_set(b"k%d" % i, b"v" * (i % 50)) for i in range(4000))       # a segment in a value
     zeros = bytes(200_000)                                                              # 9-byte empty SETs
     rng = random.Random(5)
@@ -158,8 +159,19 @@ def test_adversarial_speculation(gctx):
         parts.append(rec_set(b"key%d" % i, v[: rng.randint(1, len(v))]))
         if i % 7 == 0:
             parts.append(rec_del(b"key%d" % (i // 2)))
-    seg = b"".join(parts)
+    return b"".join(parts), inner, zeros
+
+
+def test_adversarial_speculation(gctx):
+    """Values that look like records defeat the speculative entry; results must stay exact."""
+    seg, inner, zeros = adversarial_store()
     check_parity(gctx, [seg, seg[: len(seg) // 2 + 13], inner, zeros])
+
+
+def mixed_store(key_mod=None):
+    """100 000 empty-valued SETs of k<i> (i modulo key_mod when given), seven DELs of the empty key
+    behind each."""
+    return b"".join(rec_set(b"k%d" % (i % key_mod if key_mod else i), b"") + rec_del(b"") * 7 for i in range(100_000))
 
 
 def test_pool_overflow_retry(gctx):
@@ -167,7 +179,7 @@ def test_pool_overflow_retry(gctx):
     the waves' claims run past the pool, land in its slack, the overflow is flagged, and the host
     grows the pool and replays again -- same tuples as the oracle (engine.rs:139-141 DEL records)."""
     dense = rec_del(b"") * ((8 << 20) // 5)
-    mixed = b"".join(rec_set(b"k%d" % i, b"") + rec_del(b"") * 7 for i in range(100_000))
+    mixed = mixed_store()
     gctx.set_tiles_per_stripe(1024)
     try:
         check_parity(gctx, [dense, mixed, dense[:-2]])
@@ -449,14 +461,19 @@ def test_batched_speculative_tiles(gctx, tps, change):
         gctx.set_tiles_per_stripe(0)
 
 
-def _varied_store(seed, n_bytes, del_frac, klen_rng, vlen_rng, zero_values=False, key_alphabet=None):
-    """Records of varying lengths (the candidate rounds' case): keys of random length from
-    key_alphabet (ASCII letters by default), values random or all zero."""
-    rnd = random.Random(seed)
+def _varied_key(rnd, klen_rng, key_alphabet=None):
     alpha = key_alphabet or [bytes([c]) for c in range(0x41, 0x5B)] + [bytes([c]) for c in range(0x61, 0x7B)]
+    return b"".join(rnd.choice(alpha) for _ in range(rnd.randint(*klen_rng)))
+
+
+def _varied_store(seed, n_bytes, del_frac, klen_rng, vlen_rng, zero_values=False, key_alphabet=None, key_pool=None):
+    """Records of varying lengths (the candidate rounds' case): keys of random length from
+    key_alphabet (ASCII letters by default), values random or all zero.  key_pool: a list of keys
+    to draw from instead (test_fold_paths: keys that recur)."""
+    rnd = random.Random(seed)
     out = bytearray()
     while len(out) < n_bytes:
-        k = b"".join(rnd.choice(alpha) for _ in range(rnd.randint(*klen_rng)))
+        k = rnd.choice(key_pool) if key_pool else _varied_key(rnd, klen_rng, key_alphabet)
         if rnd.random() < del_frac:
             out += rec_del(k)
         else:

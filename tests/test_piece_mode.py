@@ -68,13 +68,15 @@ BAD_UTF8 = {
 }
 
 
-def _uniform(n_rec, klen, vlen, unit=b"", change=None):
-    """n_rec SETs of one key and value length; change = (i, kind) alters record i."""
+def _uniform(n_rec, klen, vlen, unit=b"", change=None, keyf=None):
+    """n_rec SETs of one key and value length; change = (i, kind) alters record i (or a dict
+    {i: kind} for several records); keyf(i) gives record i's key of klen bytes instead of _key."""
+    changes = dict([change]) if isinstance(change, tuple) else dict(change or {})
     out = bytearray()
     for i in range(n_rec):
-        k, v = _key(i, klen, unit), _value(i, vlen)
-        if change and change[0] == i:
-            kind = change[1]
+        k, v = keyf(i) if keyf else _key(i, klen, unit), _value(i, vlen)
+        if i in changes:
+            kind = changes[i]
             if kind in BAD_UTF8:
                 bad = BAD_UTF8[kind]
                 k = (k[: klen - len(bad)] + bad) if kind == "truncated" else (k[:2] + bad + k[2 + len(bad):])[:klen]
