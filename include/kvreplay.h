@@ -216,8 +216,8 @@ int  kvr_live_keys(kvr_ctx *ctx, uint32_t flags, uint8_t *keys, uint64_t keys_ca
  * prefix16 receives 16 bytes per tuple, tag_len two words per tuple (key_tag, then key_len),
  * *n = the tuple count.  They survive every entry point that folds -- kvr_replay_live,
  * kvr_replay_last, kvr_replay_index, kvr_ingest_index, kvr_compact, kvr_compact_stage (and
- * _export / _finish after it) -- and kvr_replay, kvr_live_keys, kvr_index_fetch and kvr_get_batch
- * calls after it, until the next folding call.  It launches no kernel and changes no state.
+ * _export / _finish after it) -- and kvr_replay, kvr_live_keys, kvr_index_fetch, kvr_get_batch and
+ * kvr_put_batch calls after it, until the next folding call.  It launches no kernel and changes no state.
  * Returns KVR_OK; KVR_CAPACITY (*n set) when cap < *n; KVR_EINVAL when no folding call has run on
  * ctx, when the last one failed or had no segments, or when it kept no prefixes (a replay batched
  * past the pool-slot limit whose output outgrew its first buffer folds on the segment bytes). */
@@ -461,8 +461,63 @@ int kvr_get_batch(kvr_ctx *ctx, const uint8_t *keys, const uint64_t *key_off, si
                   int64_t *live_idx, uint64_t *val_off, uint8_t *vals, uint64_t vals_cap,
                   uint64_t *val_bytes, uint8_t *bad, uint64_t *n_crc_fail);
 int kvr_last_get_stats(const kvr_ctx *ctx, kvr_get_stats *out);
-/* 0 while ctx holds no key table; otherwise a value that changes with every index build. */
+/* 0 while ctx holds no key table; otherwise a value that changes with every index build and with
+ * every successful kvr_put_batch. */
 uint64_t kvr_index_epoch(const kvr_ctx *ctx);
+
+/* ---- batched writes: KVStore::set / delete for many operations, index updated in place ------ */
+#define KVR_OP_SET 0
+#define KVR_OP_DEL 1
+#define KVR_VALS_ON_DEVICE 0x80u   /* ops, vals, val_off are device pointers (keys: KVR_KEYS_ON_DEVICE) */
+
+typedef struct kvr_put_stats {
+    double ms_frame, ms_crc, ms_index;        /* device events on the context's stream */
+    uint64_t n_ops, n_set, n_del, bytes_out;  /* this batch */
+    uint64_t n_superseded;                    /* old live entries this batch replaced or deleted */
+    uint64_t n_live, n_slots;                 /* the index after the call */
+} kvr_put_stats;
+
+/* KVStore::set (engine.rs:157-179) / KVStore::delete (engine.rs:182-198) for n operations at
+ * once, equivalent to n successive calls in the order i = 0 .. n-1, against the index the last
+ * kvr_replay_index / kvr_ingest_index (or an earlier kvr_put_batch) left on ctx.  Operation i is
+ * ops[i] (KVR_OP_SET / KVR_OP_DEL) on key keys[key_off[i] .. key_off[i+1]) with value
+ * vals[val_off[i] .. val_off[i+1]) (the arena format of kvr_get_batch; a DEL's slice is empty).
+ *   out        receives exactly the bytes set / delete would append for this batch, *out_len of
+ *              them: [0][klen u32 LE][key][vlen u32 LE][value] per SET (engine.rs:169-173),
+ *              [1][klen u32 LE][key] per DEL (engine.rs:191-193; a DEL of an absent key still
+ *              writes its record).  The caller appends them to the active segment's file.
+ *   tuples     (optional, n entries) what kvr_replay would emit for these records: rec_off within
+ *              the active segment, seg_idx, the lengths, crc32 of the value = crc32fast::hash, the
+ *              ETag of storage.rs:27 (0 for a DEL), key_tag, op, flags 0.
+ *   *seg_off   (optional) offset of the batch within the active segment.
+ * The context owns the active segment in HBM.  The first put after an index build opens it as
+ * segment index n_segs (of that build) with id seg_id, which must exceed the last replayed
+ * segment's id; later calls with the same seg_id append to it; a larger seg_id closes it and opens
+ * the next segment index (reset_active_segment, engine.rs:209-229); a smaller one is KVR_EINVAL.
+ * Any replay-type call on ctx drops the active segments together with the index.
+ * After the call the live list, the key table and their sizes describe "old segments + active
+ * segments": kvr_index_fetch's live[] equals, tuple for tuple and in (segment, offset) order, what
+ * kvr_replay_index over those segments returns; slots[] is a valid table over it with
+ * kvr_index_slots(n_live) entries (slot placement may differ from a rebuild; no 0xFFFFFFFF entries
+ * remain).  kvr_get_batch, kvr_live_keys, kvr_index_fetch and kvr_index_find (the caller adds the
+ * active segment's host bytes to its segs[]) work on the updated state, kvr_index_epoch changes,
+ * and kvr_fold_keys_fetch's data stays as it was.  Cost: O(live keys + n); no byte of an old
+ * segment is read except for key compares.
+ * flags: KVR_KEYS_ON_DEVICE (keys, key_off), KVR_VALS_ON_DEVICE (ops, vals, val_off),
+ * KVR_OUT_ON_DEVICE (out and tuples are device pointers; tuples 16-B aligned).
+ * Returns KVR_OK; KVR_CAPACITY when out_cap < *out_len (*out_len set); KVR_EINVAL (no key table
+ * on ctx, key_off or val_off not non-decreasing, a key or value of 2^32 bytes or more,
+ * n >= 2^31-1, an op byte other than 0 or 1, a DEL with a value, a key that is not valid UTF-8 —
+ * the reference takes &str, and such a key would make the store unopenable with KVR_E_UTF8 —,
+ * NULL where a buffer is needed); < 0 otherwise.  A call that does not return KVR_OK leaves the
+ * index, the active segment, the epoch and out as they were.  n = 0 is KVR_OK and changes nothing. */
+int kvr_put_batch(kvr_ctx *ctx, uint64_t seg_id, const uint8_t *ops, const uint8_t *keys, const uint64_t *key_off,
+                  const uint8_t *vals, const uint64_t *val_off, size_t n, uint32_t flags, uint8_t *out,
+                  uint64_t out_cap, uint64_t *out_len, kvr_tuple *tuples, uint64_t *seg_off);
+int kvr_last_put_stats(const kvr_ctx *ctx, kvr_put_stats *out);
+/* The active segment kvr_put_batch keeps on ctx: its id, its segment index, the bytes appended so
+ * far and where they are in HBM (each output optional).  KVR_EINVAL when ctx holds none. */
+int kvr_active_segment(const kvr_ctx *ctx, uint64_t *seg_id, uint32_t *seg_idx, uint64_t *len, const uint8_t **d_base);
 
 #ifdef __cplusplus
 }

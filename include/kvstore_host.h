@@ -6,7 +6,7 @@
  *   kvh_gen_segment   synthetic segments, framing writer  engine.rs:157-198 (byte-identical to
  *                     kvr_gen_segment_device)
  *   kvh_fold          last-writer-wins index fold         engine.rs:137 (insert), :141 (remove)
- *   kvs_open / kvs_get / kvs_stats / kvs_compact / kvs_close
+ *   kvs_open / kvs_get / kvs_put_many / kvs_set / kvs_delete / kvs_list_keys / kvs_stats / kvs_compact / kvs_close
  *                     the crate-public KVStore surface the replay path feeds (lib.rs:2-3,
  *                     engine.rs:24, :200, :232-259); the index has the shape of the reference's
  *                     dead `Index` (src/store/index.rs:7): key -> (segment, offset, length).
@@ -141,8 +141,51 @@ int kvs_stats_get(const kvs_store *s, kvs_stats *out);
  * between the writes and the removals leaves old and new files, whose replay gives the same map.
  * Returns KVR_OK, KVR_CORRUPTED (*err) or < 0 (KVR_EIO: a file could not be written/removed). */
 int kvs_compact(kvs_store *s, kvr_ctx *ctx, uint64_t seg_target, kvr_error *err);
-/* KVStore::list_keys: up to cap keys as (offset, length) pairs into the returned arena. */
+/* stats().num_keys: the number of live keys. */
 size_t kvs_num_keys(const kvs_store *s);
+/* KVStore::list_keys (engine.rs:204-206): the live keys as an arena, in the live list's order —
+ * key i is keys[key_off[i] .. key_off[i+1]), key_off has num_keys + 1 entries, *key_bytes = the
+ * total.  KVR_CAPACITY (*key_bytes set) when keys_cap or off_cap is short. */
+int kvs_list_keys(const kvs_store *s, uint8_t *keys, uint64_t keys_cap, uint64_t *key_off, size_t off_cap,
+                  uint64_t *key_bytes);
+
+/* ---- writes: KVStore::set (engine.rs:157-179), KVStore::delete (engine.rs:182-198) -------------
+ * kvh_encode_batch: the reference's loop on one host thread — the bytes set / delete would append
+ * for n operations and the tuples kvr_replay would emit for them (rec_off from base_off, seg_idx as
+ * given, crc32 = the ETag of storage.rs:27), with the arguments, the validation and the return
+ * codes of kvr_put_batch's framing half: KVR_EINVAL (nothing written) for offsets that decrease, a
+ * key or value of 2^32 bytes or more, an op byte other than 0 / 1, a DEL with a value, a key that
+ * is not valid UTF-8, NULL where a buffer is needed; KVR_CAPACITY (*out_len set) when out_cap is
+ * short.  It is kvs_put_many's fallback and the baseline of tools/put_bench.py. */
+int kvh_encode_batch(const uint8_t *ops, const uint8_t *keys, const uint64_t *key_off, const uint8_t *vals,
+                     const uint64_t *val_off, size_t n, uint32_t seg_idx, uint64_t base_off, uint8_t *out, uint64_t out_cap,
+                     uint64_t *out_len, kvr_tuple *tuples);
+/* The host index update behind a batch whose tuples are t[0 .. n) (kvh_encode_batch's; key i is
+ * keys[key_off[i] .. key_off[i+1])): every key's last op of the batch supersedes the key's entry in
+ * live[0 .. n_live) (found through slots / segs as kvr_index_find does), the entries that remain
+ * keep their order, and the batch-last SETs follow in batch order — in place, live has room for
+ * live_cap >= n_live entries; *n_live_out = the new count (KVR_CAPACITY, nothing changed, when it
+ * exceeds live_cap).  The caller rebuilds the table with kvr_index_build_host.  One thread,
+ * O(n_live + n). */
+int kvh_index_update(kvr_tuple *live, size_t n_live, size_t live_cap, const uint32_t *slots, uint64_t n_slots,
+                     const kvr_segment *segs, const kvr_tuple *t, const uint8_t *keys, const uint64_t *key_off, size_t n,
+                     size_t *n_live_out);
+/* n set / delete operations in order (arguments as kvr_put_batch, host memory): encoded on the
+ * device (kvr_put_batch) while ctx still holds this store's key table (the epoch matches), else by
+ * kvh_encode_batch; appended to segment-<active_id>.dat with one write per batch, flushed to the OS
+ * as engine.rs:174 does; the active segment's bytes are kept as a host segment, so kvs_get and
+ * kvs_locate read the new values; the host index follows (device path: kvr_index_fetch; host path:
+ * superseded entries dropped, batch-last SETs appended, kvr_index_build_host).  Both refreshes are
+ * O(live keys) per call: batches are the intended interface.  crc_out (optional): the ETag word
+ * of value i (0 for a DEL).  stats().total_bytes and num_keys follow engine.rs:253-255.
+ * Returns KVR_OK, KVR_EINVAL, KVR_EIO (the write failed; the store is unchanged) or < 0. */
+int kvs_put_many(kvs_store *s, kvr_ctx *ctx, const uint8_t *ops, const uint8_t *keys, const uint64_t *key_off,
+                 const uint8_t *vals, const uint64_t *val_off, size_t n, uint32_t *crc_out);
+/* The n = 1 forms: KVStore::set (crc_out optional: BlobStorage::put's ETag word, storage.rs:26-35)
+ * and KVStore::delete. */
+int kvs_set(kvs_store *s, kvr_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen,
+            uint32_t *crc_out);
+int kvs_delete(kvs_store *s, kvr_ctx *ctx, const uint8_t *key, size_t klen);
 void kvs_close(kvs_store *s);
 
 #ifdef __cplusplus

@@ -223,6 +223,25 @@ struct kvr_ctx {
     hipEvent_t g_ev[5] = {};
     kvr_get_stats gstats{};
     kvr_index_stats istats{};
+    // batched puts (kvr_put_batch): the segments of the last index build (count, last id), the
+    // active segment in HBM (p_act; p_next while a call opens the following one), the segments
+    // closed since that build, the next live list and key table (swapped with lout / islots when a
+    // call succeeds) and the call's scratch
+    size_t ix_nsegs = 0;
+    uint64_t ix_last_id = 0;
+    bool p_open = false;
+    uint64_t p_epoch = 0, p_seg_id = 0, p_len = 0;
+    uint32_t p_idx = 0;
+    DevBuf<uint8_t> p_act, p_next;
+    std::vector<DevBuf<uint8_t>> p_closed;
+    SegDesc p_desc[2] = {};
+    DevBuf<kvr_tuple> p_live, p_tup;
+    DevBuf<uint32_t> p_slots, p_best, p_tag, p_slot, p_flags, p_pos, p_crc;
+    DevBuf<unsigned long long> p_tab;
+    DevBuf<uint64_t> p_koff, p_voff, p_size, p_off, p_vlen, p_nch, p_cpre, p_tot;
+    DevBuf<uint8_t> p_keys, p_vals, p_ops, p_tmp;
+    hipEvent_t p_ev[6] = {};
+    kvr_put_stats pstats{};
     DevBuf<uint8_t> ing;                   // the store's segment bytes, resident in HBM
     uint64_t ing_off = 0;
     std::vector<kvr_segment> ing_segs;     // device pointers into ing, in push order
@@ -410,6 +429,13 @@ void kvr_ctx_destroy(kvr_ctx *c) {
     c->g_vlen.release(); c->g_off.release(); c->g_src.release(); c->g_tot.release(); c->g_nch.release();
     c->g_cpre.release(); c->g_idx.release(); c->g_exp.release(); c->g_crc.release();
     for (auto &e : c->g_ev) if (e) (void)hipEventDestroy(e);
+    c->p_act.release(); c->p_next.release(); c->p_live.release(); c->p_tup.release(); c->p_slots.release();
+    for (auto &b : c->p_closed) b.release();
+    c->p_best.release(); c->p_tag.release(); c->p_slot.release(); c->p_flags.release(); c->p_pos.release();
+    c->p_crc.release(); c->p_tab.release(); c->p_koff.release(); c->p_voff.release(); c->p_size.release();
+    c->p_off.release(); c->p_vlen.release(); c->p_nch.release(); c->p_cpre.release(); c->p_tot.release();
+    c->p_keys.release(); c->p_vals.release(); c->p_ops.release(); c->p_tmp.release();
+    for (auto &e : c->p_ev) if (e) (void)hipEventDestroy(e);
     if (c->copy) (void)hipStreamSynchronize(c->copy);
     for (int i = 0; i < 2; ++i) {
         c->slot[i].release();
@@ -1793,4 +1819,5 @@ void kvr_etag_format(uint32_t crc, char *out) {
 
 #include "kvr_index.hip"
 #include "kvr_get.hip"
+#include "kvr_put.hip"
 #include "kvr_multi.hip"

@@ -1,6 +1,7 @@
 /*
  * kvr_host.cpp — host side of the drop-in (include/kvstore_host.h): discovery, the CPU
- * generator, the last-writer-wins fold and a KVStore mirror whose open() replays on the GPU.
+ * generator, the last-writer-wins fold and a KVStore mirror whose open() replays on the GPU and
+ * whose set / delete batches are encoded there (kvs_put_many; kvh_encode_batch is the host loop).
  * Built with g++ into libkvhost.so, linked against libkvreplay.so.
  */
 #include <dirent.h>
@@ -74,7 +75,7 @@ struct KeyHash {
     size_t operator()(const KeyRef &k) const { return (size_t)k.tag * 0x9E3779B97F4A7C15ull; }
 };
 struct KeyEq {
-    bool operator()(const KeyRef &a, const KeyRef &b) const { return a.n == b.n && memcmp(a.p, b.p, a.n) == 0; }
+    bool operator()(const KeyRef &a, const KeyRef &b) const { return a.n == b.n && (a.n == 0 || memcmp(a.p, b.p, a.n) == 0); }
 };
 
 }  // namespace
@@ -88,6 +89,8 @@ struct kvs_store {
     std::vector<void *> regs;                    // ranges registered for DMA (kvr_host_register)
     bool pinned = false;                         // every segment byte lies in a registered range
     std::vector<std::vector<uint8_t>> owned;     // segments written by kvs_compact
+    std::vector<uint8_t> active;                 // the bytes kvs_put_many appended to the active file
+    ptrdiff_t act_idx = -1;                      // ... as segs[act_idx] / ids[act_idx]; -1: nothing appended yet
     // the index (index.rs:5-7 shape): live keys' final SETs and the table over them
     // (kvr_replay_index / kvr_index_find)
     std::vector<kvr_tuple> live;
@@ -906,8 +909,214 @@ int kvs_compact(kvs_store *s, kvr_ctx *ctx, uint64_t seg_target, kvr_error *err)
     s->owned = std::move(new_bytes);
     s->segs.resize(n_new);
     for (size_t j = 0; j < n_new; ++j) s->segs[j] = kvr_segment{new_ids[j], s->owned[j].data(), s->owned[j].size()};
+    s->active.clear();   // the old active segment was one of the inputs; the new one is empty
+    s->act_idx = -1;
     s->drop_arena();
     return build_index(s, ctx, s->open_flags, err);
+}
+
+// ---- writes: KVStore::set / delete (engine.rs:157-198), batched ---------------------------------
+
+int kvh_encode_batch(const uint8_t *ops, const uint8_t *keys, const uint64_t *key_off, const uint8_t *vals,
+                     const uint64_t *val_off, size_t n, uint32_t seg_idx, uint64_t base_off, uint8_t *out, uint64_t out_cap,
+                     uint64_t *out_len, kvr_tuple *tuples) {
+    if (!out_len) return KVR_EINVAL;
+    *out_len = 0;
+    if (n == 0) return KVR_OK;
+    if (n >= 0x7FFFFFFFull || !ops || !key_off || !val_off || (out_cap && !out)) return KVR_EINVAL;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) {   // everything is checked before a byte is written
+        if (key_off[i + 1] < key_off[i] || key_off[i + 1] - key_off[i] >= (1ull << 32)) return KVR_EINVAL;
+        if (val_off[i + 1] < val_off[i] || val_off[i + 1] - val_off[i] >= (1ull << 32)) return KVR_EINVAL;
+        if (ops[i] > 1 || (ops[i] == KVR_OP_DEL && val_off[i + 1] != val_off[i])) return KVR_EINVAL;
+        total += 5 + (key_off[i + 1] - key_off[i]) + (ops[i] == KVR_OP_SET ? 4 + (val_off[i + 1] - val_off[i]) : 0);
+    }
+    if ((key_off[n] && !keys) || (val_off[n] && !vals)) return KVR_EINVAL;
+    for (size_t i = 0; i < n; ++i)   // the reference takes &str (engine.rs:157, :182)
+        if (!utf8_valid(keys + key_off[i], (size_t)(key_off[i + 1] - key_off[i]))) return KVR_EINVAL;
+    *out_len = total;
+    if (total > out_cap) return KVR_CAPACITY;
+    uint64_t o = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t klen = (uint32_t)(key_off[i + 1] - key_off[i]), vlen = (uint32_t)(val_off[i + 1] - val_off[i]);
+        const uint8_t *k = keys + key_off[i], *v = vals + val_off[i];
+        uint8_t *q = out + o;
+        q[0] = ops[i];                                  // engine.rs:169 / :191
+        memcpy(q + 1, &klen, 4);                        // (little-endian hosts, as the replay's readers)
+        if (klen) memcpy(q + 5, k, klen);
+        uint64_t sz = 5 + (uint64_t)klen;
+        if (ops[i] == KVR_OP_SET) {
+            memcpy(q + 5 + klen, &vlen, 4);
+            if (vlen) memcpy(q + 9 + klen, v, vlen);
+            sz += 4 + (uint64_t)vlen;
+        }
+        if (tuples) {
+            kvr_tuple &t = tuples[i];
+            memset(&t, 0, sizeof(t));
+            t.rec_off = base_off + o;
+            t.seg_idx = seg_idx;
+            t.key_len = klen;
+            t.val_len = ops[i] == KVR_OP_SET ? vlen : 0;
+            t.crc32 = ops[i] == KVR_OP_SET ? crc32_update(0, v, vlen) : 0;
+            t.key_tag = crc32_update(0, k, klen);
+            t.op = ops[i];
+        }
+        o += sz;
+    }
+    return KVR_OK;
+}
+
+int kvh_index_update(kvr_tuple *live, size_t n_live, size_t live_cap, const uint32_t *slots, uint64_t n_slots,
+                     const kvr_segment *segs, const kvr_tuple *t, const uint8_t *keys, const uint64_t *key_off, size_t n,
+                     size_t *n_live_out) {
+    if (!n_live_out || (n && (!t || !key_off)) || (n_live && (!live || !slots || !segs)) || live_cap < n_live) return KVR_EINVAL;
+    *n_live_out = n_live;
+    std::unordered_map<KeyRef, size_t, KeyHash, KeyEq> last;   // every key's last op of the batch
+    last.reserve(n * 2 + 16);
+    for (size_t i = 0; i < n; ++i) last[KeyRef{keys + key_off[i], t[i].key_len, t[i].key_tag}] = i;
+    std::vector<uint8_t> dead(n_live, 0), add(n, 0);
+    size_t n_add = 0, n_dead = 0;
+    for (const auto &kv : last) {
+        const size_t i = kv.second;
+        if (n_live) {
+            const int64_t j = kvr_index_find(live, slots, n_slots, segs, kv.first.p, kv.first.n);
+            if (j >= 0) { dead[(size_t)j] = 1; ++n_dead; }
+        }
+        add[i] = t[i].op == KVR_OP_SET;
+        n_add += add[i];
+    }
+    *n_live_out = n_live - n_dead + n_add;
+    if (*n_live_out > live_cap) return KVR_CAPACITY;   // (nothing changed yet)
+    size_t w = 0;
+    for (size_t j = 0; j < n_live; ++j)
+        if (!dead[j]) live[w++] = live[j];
+    for (size_t i = 0; i < n; ++i)
+        if (add[i]) live[w++] = t[i];
+    return KVR_OK;
+}
+
+// the store's host index after a batch (the host path of kvs_put_many)
+static int host_index_update(kvs_store *s, const kvr_tuple *t, const uint8_t *keys, const uint64_t *key_off, size_t n) {
+    const size_t n_live = s->live.size();
+    size_t n_new = 0;
+    s->live.resize(n_live + n);
+    int rc = kvh_index_update(s->live.data(), n_live, s->live.size(), s->slots.data(), s->slots.size(), s->segs.data(), t,
+                              keys, key_off, n, &n_new);
+    if (rc != KVR_OK) { s->live.resize(n_live); return rc; }
+    s->live.resize(n_new);
+    s->slots.assign(kvr_index_slots(n_new), 0u);
+    s->epoch = 0;   // built here: the context holds no table of this state
+    return kvr_index_build_host(s->live.data(), n_new, s->slots.data(), s->slots.size());
+}
+
+int kvs_put_many(kvs_store *s, kvr_ctx *ctx, const uint8_t *ops, const uint8_t *keys, const uint64_t *key_off,
+                 const uint8_t *vals, const uint64_t *val_off, size_t n, uint32_t *crc_out) {
+    if (!s) return KVR_EINVAL;
+    if (n == 0) return KVR_OK;
+    if (!ops || !key_off || !val_off) return KVR_EINVAL;
+    const bool opened = s->act_idx >= 0;
+    const uint32_t seg_idx = (uint32_t)(opened ? (size_t)s->act_idx : s->segs.size());
+    const uint64_t base_off = s->active.size();
+    // 1. the bytes and the tuples: on the device while ctx holds this store's key table
+    std::vector<kvr_tuple> t(n);
+    std::vector<uint8_t> rec;
+    uint64_t out_len = 0;
+    const bool device = ctx && s->epoch && kvr_index_epoch(ctx) == s->epoch;
+    int rc;
+    if (device) {
+        uint64_t cap = 0;
+        for (size_t i = 0; i < n; ++i) {   // (sizes of valid input; an invalid one fails in the call)
+            if (key_off[i + 1] < key_off[i] || val_off[i + 1] < val_off[i]) return KVR_EINVAL;
+            cap += 9 + (key_off[i + 1] - key_off[i]) + (val_off[i + 1] - val_off[i]);
+        }
+        rec.resize(cap);
+        uint64_t so = 0;
+        rc = kvr_put_batch(ctx, s->active_id, ops, keys, key_off, vals, val_off, n, 0, rec.data(), rec.size(), &out_len,
+                           t.data(), &so);
+        if (rc == KVR_OK && (so != base_off || (n && t[0].seg_idx != seg_idx))) {   // not this store's active segment
+            s->epoch = 0;
+            return KVR_EINVAL;
+        }
+    } else {
+        rc = kvh_encode_batch(ops, keys, key_off, vals, val_off, n, seg_idx, base_off, nullptr, 0, &out_len, nullptr);
+        if (rc == KVR_CAPACITY) {
+            rec.resize(out_len);
+            rc = kvh_encode_batch(ops, keys, key_off, vals, val_off, n, seg_idx, base_off, rec.data(), rec.size(), &out_len,
+                                  t.data());
+        }
+    }
+    if (rc != KVR_OK) return rc;
+    // 2. one write per batch to the active file, flushed to the OS as engine.rs:174 does (no fsync)
+    const std::string ap = s->dir + "/segment-" + std::to_string(s->active_id) + ".dat";
+    const int fd = open(ap.c_str(), O_WRONLY | O_CREAT | O_APPEND, 0644);
+    bool ok = fd >= 0;
+    for (uint64_t o = 0; ok && o < out_len;) {
+        const ssize_t w = write(fd, rec.data() + o, (size_t)(out_len - o));
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) ok = false;
+        else o += (uint64_t)w;
+    }
+    if (!ok) {   // the store stays as it was: the file is cut back, the device's newer table is forgotten
+        if (fd >= 0) { (void)!ftruncate(fd, (off_t)base_off); close(fd); }
+        if (device) s->epoch = 0;
+        return KVR_EIO;
+    }
+    close(fd);
+    // 3. the active segment's bytes as a host segment (kvs_get / kvs_locate read new values there)
+    s->active.insert(s->active.end(), rec.begin(), rec.begin() + (ptrdiff_t)out_len);
+    if (!opened) {
+        s->act_idx = (ptrdiff_t)s->segs.size();
+        s->ids.push_back(s->active_id);
+        s->segs.push_back(kvr_segment{s->active_id, nullptr, 0});
+    }
+    s->segs[(size_t)s->act_idx].bytes = s->active.data();
+    s->segs[(size_t)s->act_idx].len = s->active.size();
+    // 4. the host index: fetched from the device, or updated here
+    if (device) {
+        kvr_put_stats ps{};
+        kvr_last_put_stats(ctx, &ps);
+        s->live.resize(ps.n_live);
+        s->slots.resize(ps.n_slots);
+        rc = kvr_index_fetch(ctx, 0, s->live.data(), s->live.size(), s->slots.data(), s->slots.size());
+        if (rc != KVR_OK) return rc;
+        s->epoch = kvr_index_epoch(ctx);
+    } else {
+        rc = host_index_update(s, t.data(), keys, key_off, n);
+        if (rc != KVR_OK) return rc;
+    }
+    finish_index(s);
+    if (crc_out)
+        for (size_t i = 0; i < n; ++i) crc_out[i] = t[i].crc32;
+    return KVR_OK;
+}
+
+int kvs_set(kvs_store *s, kvr_ctx *ctx, const uint8_t *key, size_t klen, const uint8_t *val, size_t vlen, uint32_t *crc_out) {
+    const uint8_t op = KVR_OP_SET;
+    const uint64_t ko[2] = {0, klen}, vo[2] = {0, vlen};
+    return kvs_put_many(s, ctx, &op, key, ko, val, vo, 1, crc_out);
+}
+
+int kvs_delete(kvs_store *s, kvr_ctx *ctx, const uint8_t *key, size_t klen) {
+    const uint8_t op = KVR_OP_DEL;
+    const uint64_t ko[2] = {0, klen}, vo[2] = {0, 0};
+    return kvs_put_many(s, ctx, &op, key, ko, nullptr, vo, 1, nullptr);
+}
+
+int kvs_list_keys(const kvs_store *s, uint8_t *keys, uint64_t keys_cap, uint64_t *key_off, size_t off_cap, uint64_t *key_bytes) {
+    if (!s || !key_bytes || (keys_cap && !keys) || (off_cap && !key_off)) return KVR_EINVAL;
+    uint64_t total = 0;
+    for (const kvr_tuple &t : s->live) total += t.key_len;
+    *key_bytes = total;
+    if (total > keys_cap || s->live.size() + 1 > off_cap) return KVR_CAPACITY;
+    uint64_t o = 0;
+    for (size_t j = 0; j < s->live.size(); ++j) {
+        const kvr_tuple &t = s->live[j];
+        key_off[j] = o;
+        if (t.key_len) memcpy(keys + o, s->segs[t.seg_idx].bytes + t.rec_off + 5, t.key_len);
+        o += t.key_len;
+    }
+    key_off[s->live.size()] = o;
+    return KVR_OK;
 }
 
 void kvs_close(kvs_store *s) { delete s; }

@@ -194,6 +194,8 @@ int kvr_replay_index(kvr_ctx *c, const kvr_segment *segs, size_t n, uint32_t fla
     c->ix_slots = ns;
     c->ix_valid = true;
     c->ix_epoch = ++index_epochs;   // kvr_index_epoch: no other build in this process has this value
+    c->ix_nsegs = n;                // kvr_put_batch opens its active segment behind these
+    c->ix_last_id = n ? segs[n - 1].seg_id : 0;
     c->istats.n_live = total;
     c->istats.n_slots = ns;
     c->istats.fold_rounds = c->fold_rounds;

@@ -3,6 +3,7 @@
 This mirrors the reference's replay surface (whispem/mini-kvstore-v2):
   KVStore.open(dir)   -> src/store/engine.rs:24   (index rebuild on restart, replay on the GPU)
   KVStore.get(key)    -> engine.rs:200
+  KVStore.set / delete / put_many / list_keys -> engine.rs:157, :182, :204 (batched on the GPU)
   KVStore.stats()     -> engine.rs:237-259 (StoreStats, src/store/stats.rs:3-10)
   CorruptedData       -> StoreError::CorruptedData (src/store/error.rs:11-12), same messages
 and exposes the engine itself (Context.replay) plus the synthetic generator.
@@ -28,6 +29,8 @@ E_NONE, E_OPEN, E_KEY_LEN, E_KEY, E_UTF8, E_VAL_LEN, E_VAL, E_OPCODE = range(8)
 KIND_NAMES = {0: "NONE", 1: "OPEN", 2: "KEY_LEN", 3: "KEY", 4: "UTF8", 5: "VAL_LEN", 6: "VAL", 7: "OPCODE"}
 SEGS_ON_DEVICE, OUT_ON_DEVICE, EXPECTED_ON_DEVICE, HOST_PINNED = 0x1, 0x2, 0x4, 0x8
 KEYS_ON_DEVICE, GET_LOCATE_ONLY, GET_VERIFY = 0x10, 0x20, 0x40
+VALS_ON_DEVICE = 0x80
+OP_SET, OP_DEL = 0, 1
 TF_VERIFIED, TF_CRC_FAIL = 0x1, 0x2
 
 TUPLE_DTYPE = np.dtype([("rec_off", "<u8"), ("seg_idx", "<u4"), ("key_len", "<u4"), ("val_len", "<u4"),
@@ -71,6 +74,12 @@ class GetStats(C.Structure):
     _fields_ = [("ms_probe", C.c_double), ("ms_gather", C.c_double), ("ms_verify", C.c_double),
                 ("n_keys", C.c_uint64), ("n_found", C.c_uint64), ("val_bytes", C.c_uint64),
                 ("n_crc_fail", C.c_uint64)]
+
+
+class PutStats(C.Structure):
+    _fields_ = [("ms_frame", C.c_double), ("ms_crc", C.c_double), ("ms_index", C.c_double),
+                ("n_ops", C.c_uint64), ("n_set", C.c_uint64), ("n_del", C.c_uint64), ("bytes_out", C.c_uint64),
+                ("n_superseded", C.c_uint64), ("n_live", C.c_uint64), ("n_slots", C.c_uint64)]
 
 
 class GenParams(C.Structure):
@@ -167,6 +176,15 @@ def _load():
     rep.kvr_last_get_stats.argtypes = [P, C.POINTER(GetStats)]
     rep.kvr_index_epoch.argtypes = [P]
     rep.kvr_index_epoch.restype = U64
+    rep.kvr_put_batch.argtypes = [P, U64, P, P, P, P, P, SZ, U32, P, U64, C.POINTER(U64), P, C.POINTER(U64)]
+    rep.kvr_last_put_stats.argtypes = [P, C.POINTER(PutStats)]
+    rep.kvr_active_segment.argtypes = [P, C.POINTER(U64), C.POINTER(U32), C.POINTER(U64), C.POINTER(P)]
+    host.kvh_encode_batch.argtypes = [P, P, P, P, P, SZ, U32, U64, P, U64, C.POINTER(U64), P]
+    host.kvh_index_update.argtypes = [P, SZ, SZ, P, U64, C.POINTER(Segment), P, P, P, SZ, C.POINTER(SZ)]
+    host.kvs_put_many.argtypes = [P, P, P, P, P, P, P, SZ, P]
+    host.kvs_set.argtypes = [P, P, P, SZ, P, SZ, C.POINTER(U32)]
+    host.kvs_delete.argtypes = [P, P, P, SZ]
+    host.kvs_list_keys.argtypes = [P, P, U64, P, SZ, C.POINTER(U64)]
     rep.kvr_index_slots.argtypes = [U64]
     rep.kvr_index_slots.restype = U64
     rep.kvr_index_hash.argtypes = [U32]
@@ -389,6 +407,49 @@ class GetResult:
         if self.values is None:
             raise ValueError("no value bytes were gathered (values=False or device outputs)")
         return self.values[int(self.val_off[i]): int(self.val_off[i + 1])].tobytes()
+
+
+def op_arena(ops):
+    """A list of (key, value) pairs, value None meaning DEL -> (op bytes uint8, key arena, key offsets,
+    value arena, value offsets): the input arrays of kvr_put_batch / kvh_encode_batch."""
+    ops = list(ops)
+    keys, koff = key_arena([k for k, _ in ops])
+    vals, voff = key_arena([b"" if v is None else v for _, v in ops])
+    return np.array([OP_DEL if v is None else OP_SET for _, v in ops], dtype=np.uint8), keys, koff, vals, voff
+
+
+@dataclass
+class PutResult:
+    """kvr_put_batch's answer.  data (the bytes to append to the active segment's file) and tuples
+    are None where they stayed in device memory (out_ptrs) or the call did not return KVR_OK;
+    seg_idx / seg_off: where the batch lies (the active segment's index, the offset in it)."""
+    status: int
+    data: bytes | None
+    tuples: np.ndarray | None
+    seg_idx: int
+    seg_off: int
+    stats: PutStats | None
+    out_len: int = 0
+
+
+def host_encode_batch(ops, seg_idx=0, base_off=0, out_cap=None):
+    """kvh_encode_batch: the reference's set / delete loop on the host over ops (a list of (key, value)
+    pairs, value None = DEL, or the arrays of op_arena) -> PutResult (stats None)."""
+    _, host = _load()
+    o, keys, koff, vals, voff = ops if isinstance(ops, tuple) else op_arena(ops)
+    n = len(o)
+    ol = C.c_uint64()
+    cap = out_cap if out_cap is not None else int(5 * n + 4 * n + (koff[-1] if n else 0) + (voff[-1] if n else 0))
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    tup = np.zeros(max(n, 1), dtype=TUPLE_DTYPE)
+    rc = host.kvh_encode_batch(o.ctypes.data if n else None, keys.ctypes.data if keys.size else None, koff.ctypes.data,
+                               vals.ctypes.data if vals.size else None, voff.ctypes.data, n, seg_idx, base_off,
+                               out.ctypes.data, cap, C.byref(ol), tup.ctypes.data)
+    if rc not in (OK, CAPACITY, EINVAL):
+        raise NativeError(f"kvh_encode_batch: {rc}")
+    ok = rc == OK
+    return PutResult(rc, out[: ol.value].tobytes() if ok else None, tup[:n] if ok else None, seg_idx, base_off, None,
+                     int(ol.value))
 
 
 class CompactResult:
@@ -830,6 +891,80 @@ class Context:
         return GetResult(rc, idx[:n], voff, vals[: vb.value] if values and rc == OK else None, int(nf.value),
                          bad[:n] if verify else None, self.last_get_stats(), int(vb.value))
 
+    def index_fetch(self, segments=None):
+        """kvr_index_fetch: the live list and the key table the context holds now (after
+        replay_index / ingest_index and any put_batch since) -> Index.  segments: the host bytes
+        Index.find compares keys in (the old segments plus the active ones)."""
+        if self.active_segment() is not None:
+            st = self.last_put_stats()
+        else:
+            st = IndexStats()
+            self._rep.kvr_last_index_stats(self.h, C.byref(st))
+        live = np.zeros(max(st.n_live, 1), dtype=TUPLE_DTYPE)
+        slots = np.zeros(max(st.n_slots, 1), dtype=np.uint32)
+        rc = self._rep.kvr_index_fetch(self.h, 0, live.ctypes.data, st.n_live, slots.ctypes.data, st.n_slots)
+        if rc != OK:
+            raise NativeError(f"kvr_index_fetch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        return Index(live[: st.n_live], slots[: st.n_slots], segments, st)
+
+    def last_put_stats(self) -> PutStats:
+        s = PutStats()
+        self._rep.kvr_last_put_stats(self.h, C.byref(s))
+        return s
+
+    def active_segment(self):
+        """kvr_active_segment: (seg_id, seg_idx, length, device pointer) of the active segment
+        put_batch keeps on the context, or None when it holds none."""
+        sid, idx, ln, p = C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_void_p()
+        if self._rep.kvr_active_segment(self.h, C.byref(sid), C.byref(idx), C.byref(ln), C.byref(p)) != OK:
+            return None
+        return int(sid.value), int(idx.value), int(ln.value), int(p.value or 0)
+
+    def put_batch(self, ops, seg_id, keys_ptr=None, out_ptrs=None, out_cap=None):
+        """KVStore::set / delete for many operations at once against the index on the device
+        (kvr_put_batch).  ops: a list of (key, value) pairs, value None meaning DEL (or the arrays
+        of op_arena); or keys_ptr = (ops, keys, key offsets, values, value offsets, n) device
+        pointers with everything already in HBM.  out_ptrs = (out, out_cap, tuples or None) device
+        pointers keeps the outputs in HBM.  Host outputs are sized exactly unless out_cap is given.
+        KVR_EINVAL and KVR_CAPACITY come back as the status.  Returns PutResult."""
+        flags = 0
+        if keys_ptr is not None:
+            op_p, kp, kop, vp, vop, n = keys_ptr
+            flags |= KEYS_ON_DEVICE | VALS_ON_DEVICE
+            keep, need = None, None
+        else:
+            o, keys, koff, vals, voff = ops if isinstance(ops, tuple) else op_arena(ops)
+            o = np.ascontiguousarray(o, dtype=np.uint8)
+            keys, vals = np.ascontiguousarray(keys, dtype=np.uint8), np.ascontiguousarray(vals, dtype=np.uint8)
+            koff, voff = np.ascontiguousarray(koff, dtype=np.uint64), np.ascontiguousarray(voff, dtype=np.uint64)
+            n = len(o)
+            op_p, kp, kop = (o.ctypes.data if n else None), (keys.ctypes.data if keys.size else None), koff.ctypes.data
+            vp, vop = (vals.ctypes.data if vals.size else None), voff.ctypes.data
+            keep = (o, keys, koff, vals, voff)
+            need = int(9 * n + (koff[-1] if n else 0) + (voff[-1] if n else 0))
+        ol, so = C.c_uint64(), C.c_uint64()
+        out = tup = None
+        if out_ptrs is not None:
+            outp, cap, tp = out_ptrs
+            flags |= OUT_ON_DEVICE
+        else:
+            cap = out_cap if out_cap is not None else need
+            if cap is None:
+                raise ValueError("device inputs with host outputs need out_cap")
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            tup = np.zeros(max(n, 1), dtype=TUPLE_DTYPE)
+            outp, tp = out.ctypes.data, tup.ctypes.data
+        rc = self._rep.kvr_put_batch(self.h, seg_id, op_p, kp, kop, vp, vop, n, flags, outp, cap, C.byref(ol), tp,
+                                     C.byref(so))
+        if rc not in (OK, CAPACITY, EINVAL):
+            raise NativeError(f"kvr_put_batch: {self._rep.kvr_strerror(rc).decode()} ({rc})")
+        del keep
+        ok = rc == OK
+        act = self.active_segment() if ok else None
+        return PutResult(rc, out[: ol.value].tobytes() if ok and out is not None else None,
+                         tup[:n] if ok and tup is not None else None, act[1] if act else 0, int(so.value),
+                         self.last_put_stats() if ok else None, int(ol.value))
+
     def etag_batch(self, data, offs, lens, expected=None, on_device=False, data_len=None):
         """Batch ETag (kvr_etag_batch): CRC-32 of data[offs[i]:offs[i]+lens[i]] for every i.
         data is bytes / a uint8 array, or a device pointer with on_device=True (then data_len).
@@ -1033,6 +1168,31 @@ def host_get_many(index, keys, threads=1, segments=None, vals_cap=None):
     return GetResult(rc, idx[:n], voff, vals[: vb.value] if rc == OK else None, 0, None, None, int(vb.value))
 
 
+def host_index_update(index, segments, tuples, keys):
+    """kvh_index_update + kvr_index_build_host: the host index after a batch whose tuples are
+    tuples (host_encode_batch's) and whose keys are keys ((arena, offsets), or a list) -> Index over
+    segments (host bytes: the old segments and the active one)."""
+    rep, host = _load()
+    arrs = [np.frombuffer(s, dtype=np.uint8) if isinstance(s, (bytes, bytearray)) else np.ascontiguousarray(s)
+            for s in segments]
+    cs = (Segment * max(len(arrs), 1))(*[Segment(i, a.ctypes.data if a.size else None, a.size)
+                                         for i, a in enumerate(arrs)])
+    arena, offs = keys if isinstance(keys, tuple) else key_arena(keys)
+    arena, offs = np.ascontiguousarray(arena, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+    t = np.ascontiguousarray(tuples, dtype=TUPLE_DTYPE)
+    n, nl = len(t), len(index.live)
+    live = np.zeros(max(nl + n, 1), dtype=TUPLE_DTYPE)
+    live[:nl] = index.live
+    out = C.c_size_t()
+    rc = host.kvh_index_update(live.ctypes.data, nl, len(live), index.slots.ctypes.data, len(index.slots), cs,
+                               t.ctypes.data if n else None, arena.ctypes.data if arena.size else None, offs.ctypes.data,
+                               n, C.byref(out))
+    if rc != OK:
+        raise NativeError(f"kvh_index_update: {rc}")
+    live = live[: out.value]
+    return Index(live, index_build_host(live), segments, None)
+
+
 def index_hash(tag):
     rep, _ = _load()
     return int(rep.kvr_index_hash(tag))
@@ -1092,6 +1252,57 @@ class KVStore:
         if rc != OK:
             raise NativeError(f"kvs_get_many: {rc}")
         return [vals[int(voff[i]): int(voff[i + 1])].tobytes() if idx[i] >= 0 else None for i in range(n)]
+
+    def put_many(self, ops, device=True):
+        """set / delete for a list of (key, value) pairs in order, value None meaning delete
+        (kvs_put_many) -> the ETag words (CRC-32 of each value, 0 for a delete).  device=True lets
+        the GPU encode the batch and update the index while the store's context still holds the
+        store's key table; otherwise the host does.  Same bytes and the same index either way."""
+        o, keys, koff, vals, voff = op_arena(ops)
+        n = len(o)
+        ctx = self._ctx.h if device and self._ctx is not None else None
+        crc = np.zeros(max(n, 1), dtype=np.uint32)
+        rc = self._host.kvs_put_many(self._h, ctx, o.ctypes.data if n else None, keys.ctypes.data if keys.size else None,
+                                     koff.ctypes.data, vals.ctypes.data if vals.size else None, voff.ctypes.data, n,
+                                     crc.ctypes.data)
+        if rc != OK:
+            raise NativeError(f"kvs_put_many: {rc}")
+        return [int(x) for x in crc[:n]]
+
+    def set(self, key, value, device=True):
+        """KVStore::set (engine.rs:157) -> the value's ETag word (BlobStorage::put, storage.rs:27)."""
+        kb = key.encode() if isinstance(key, str) else bytes(key)
+        k, v = np.frombuffer(kb, dtype=np.uint8), np.frombuffer(bytes(value), dtype=np.uint8)
+        crc = C.c_uint32()
+        ctx = self._ctx.h if device and self._ctx is not None else None
+        rc = self._host.kvs_set(self._h, ctx, k.ctypes.data if k.size else None, k.size,
+                                v.ctypes.data if v.size else None, v.size, C.byref(crc))
+        if rc != OK:
+            raise NativeError(f"kvs_set: {rc}")
+        return int(crc.value)
+
+    def delete(self, key, device=True):
+        """KVStore::delete (engine.rs:182)."""
+        kb = key.encode() if isinstance(key, str) else bytes(key)
+        k = np.frombuffer(kb, dtype=np.uint8)
+        ctx = self._ctx.h if device and self._ctx is not None else None
+        rc = self._host.kvs_delete(self._h, ctx, k.ctypes.data if k.size else None, k.size)
+        if rc != OK:
+            raise NativeError(f"kvs_delete: {rc}")
+
+    def list_keys(self):
+        """KVStore::list_keys (engine.rs:204): the live keys as bytes, in the live list's order."""
+        kb = C.c_uint64()
+        n = int(self._host.kvs_num_keys(self._h))
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        rc = self._host.kvs_list_keys(self._h, None, 0, offs.ctypes.data, 0, C.byref(kb))
+        if rc not in (OK, CAPACITY):
+            raise NativeError(f"kvs_list_keys: {rc}")
+        keys = np.zeros(max(kb.value, 1), dtype=np.uint8)
+        rc = self._host.kvs_list_keys(self._h, keys.ctypes.data, keys.size, offs.ctypes.data, offs.size, C.byref(kb))
+        if rc != OK:
+            raise NativeError(f"kvs_list_keys: {rc}")
+        return [keys[int(offs[i]): int(offs[i + 1])].tobytes() for i in range(n)]
 
     def locate(self, key):
         kb = key.encode() if isinstance(key, str) else bytes(key)
